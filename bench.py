@@ -9,7 +9,16 @@ fixed as N grows ("scaling": "strong"). One step = one bq_enrich launch over
 the rank's shard (reads 5 inputs, writes 14 columns). Ranks share no data
 (symbols are independent); the only collective is the MAX of the timings.
 
-Also reported (same JSON line):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: set up,
+warm up, time the K steps, print the JSON line (headline figure, ms_per_step
+and the kernel's roofline from the HIP events of the same K steps).
+`--dump-outputs DIR` writes what the last timed step computed, the 14 columns
+the caller of enrich receives, as DIR/<column>.npy (float64; a fixed, seeded
+sample of whole symbol rows when the columns exceed the dump budget, from
+the end of the indicator warm-up on, so that every value is finite; the
+inputs are seeded, so two builds are comparable output for output).
+
+With `--full` the same JSON line also reports (each leg has its --no-* switch):
   roofline     — algorithmic bytes (152 B/candle) / mean enrich_kernel time
                  (HIP events on the launch stream) vs 8 TB/s HBM peak; traffic
                  from the committed rocprofv3 PMC summary of this workload;
@@ -73,6 +82,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--symbols", type=int, default=100_000, help="total symbols, sharded over the ranks")
     ap.add_argument("--candles", type=int, default=10_000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (breadth, shard, tick, store, rows, live, "
+                         "cohort, cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output columns as DIR/<column>.npy")
     ap.add_argument("--shard-symbols", type=int, default=12_500, help="per-GPU symbols of the weak-scaling leg")
     ap.add_argument("--shard-steps", type=int, default=10)
     ap.add_argument("--no-shard", action="store_true")
@@ -679,9 +693,63 @@ def bench_store(args, dev):
     }
 
 
-def time_enrich(panel, steps: int, warmup: int, world: int):
+DUMP_BUDGET_BYTES = 48 << 20   # all columns of one rank together (the limit on a dump is 64 MB)
+DUMP_SEED = 20240607
+
+
+def indicator_warmup(params=None) -> int:
+    """Candles at the start of every symbol in which some column of the set
+    is NaN by definition (its window is not full yet): the longest window."""
+    p = params or engine.IndicatorParams()
+    return max(*p.ma_periods, p.rsi_window, p.bb_window, p.atr_window, p.twap_window, p.mfi_window)
+
+
+def dump_outputs(out, path: str, world: int, rank: int, first: int = 0) -> dict:
+    """Write the columns of `out` (what the last timed enrich step returned)
+    as path/<column>.npy, float64 (path/<column>_rank<r>.npy at N > 1, each
+    rank its shard), from candle `first` on: the benchmark passes the
+    indicator warm-up, so the files hold computed values only and none of the
+    NaNs that stand for a window not yet full (a panel no longer than the
+    warm-up is written whole). Columns larger than the budget are sampled: whole symbol
+    rows drawn once from a fixed seed (sorted, the same rows for every column
+    and every run with the same arguments), and, only when one row of all
+    columns alone exceeds the budget, a fixed draw of candle positions too."""
+    os.makedirs(path, exist_ok=True)
+    S, T_all = next(iter(out.values())).shape
+    first = first if 0 <= first < T_all else 0
+    out = {k: v[:, first:] for k, v in out.items()}
+    T = T_all - first
+    budget = DUMP_BUDGET_BYTES // max(1, world)
+    row_bytes = 8 * T * len(out)
+    rng = np.random.default_rng(DUMP_SEED + rank)
+    n_rows = min(S, max(1, budget // row_bytes))
+    n_cols = min(T, max(1, budget // (8 * len(out) * n_rows)))
+    rows = np.sort(rng.choice(S, n_rows, replace=False)) if n_rows < S else np.arange(S)
+    if 2 <= n_rows < S:
+        rows[0], rows[-1] = 0, S - 1   # the panel's first and last symbol are always in the sample
+    cols = np.sort(rng.choice(T, n_cols, replace=False)) if n_cols < T else None
+    dev = next(iter(out.values())).device
+    ridx = torch.from_numpy(rows).to(dev)
+    cidx = None if cols is None else torch.from_numpy(cols).to(dev)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    total = nonfinite = 0
+    for k, v in out.items():
+        a = v.index_select(0, ridx)
+        if cidx is not None:
+            a = a.index_select(1, cidx)
+        a = np.ascontiguousarray(a.cpu().numpy(), dtype=np.float64)
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), a)
+        total += a.nbytes
+        nonfinite += int(a.size - np.isfinite(a).sum())
+    return {"dir": path, "columns": len(out), "rows": int(n_rows), "of_rows": int(S),
+            "candles": int(n_cols), "of_candles": int(T_all), "first_candle": int(first),
+            "bytes": int(total), "nonfinite": nonfinite, "seed": DUMP_SEED}
+
+
+def time_enrich(panel, steps: int, warmup: int, world: int, keep_out: bool = False):
     """Wall time per step (barrier + synchronize on both sides, max over
-    ranks) and mean enrich_kernel time (HIP events on the launch stream)."""
+    ranks) and mean enrich_kernel time (HIP events on the launch stream);
+    with keep_out also the output columns as the last step left them."""
     S, T = panel["close"].shape
     dev = panel["close"].device
     out = engine.enrich_outputs(S, T, dev)   # padded row pitch (engine.enrich_outputs)
@@ -702,8 +770,9 @@ def time_enrich(panel, steps: int, warmup: int, world: int):
     barrier(world)
     wall = time.perf_counter() - t0
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    del out
-    return max_over_ranks(wall, world) / steps, max_over_ranks(kern_ms, world)
+    if not keep_out:
+        out = None
+    return max_over_ranks(wall, world) / steps, max_over_ranks(kern_ms, world), out
 
 
 def main():
@@ -716,7 +785,11 @@ def main():
     lo, hi = shard_bounds(args.symbols, world, rank)
     S, T = hi - lo, args.candles
     panel = device_panel(S, T, device=dev, seed=1234 + rank)
-    step_s, kern_ms = time_enrich(panel, args.steps, args.warmup, world)
+    step_s, kern_ms, out = time_enrich(panel, args.steps, args.warmup, world, keep_out=bool(args.dump_outputs))
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(out, args.dump_outputs, world, rank, first=indicator_warmup())
+    del out
     value = args.symbols * T / step_s
     bytes_launch = S * T * BYTES_PER_CANDLE
     achieved = bytes_launch / (kern_ms * 1e-3) / 1e9
@@ -758,13 +831,15 @@ def main():
             "candles_per_launch": S * T,
         },
     }
-    if not args.no_breadth:
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    if args.full and not args.no_breadth:
         result["breadth"] = bench_breadth(args, panel, world, dev)
     del panel
     torch.cuda.empty_cache()
-    if not args.no_shard:
+    if args.full and not args.no_shard:
         shard = device_panel(args.shard_symbols, T, device=dev, seed=4321 + rank)
-        sh_step, sh_kern = time_enrich(shard, args.shard_steps, 2, world)
+        sh_step, sh_kern, _ = time_enrich(shard, args.shard_steps, 2, world)
         result["shard"] = {
             "workload": f"C4 shard: {args.shard_symbols} symbols x {T} candles per GPU (weak scaling)",
             "value": args.shard_symbols * T * world / sh_step,
@@ -781,14 +856,15 @@ def main():
     # they run at every world size; the per-row legs at N = 1 only; the CPU
     # baseline at every world size (north_star: the reference CPU path beside
     # the GPU figure at 1, 2, 4 and 8 GPUs)
-    if rank == 0 and not args.no_tick:
+    if args.full and rank == 0 and not args.no_tick:
         result["tick"] = bench_tick(args, dev)
         result["store"] = bench_store(args, dev)
-    if rank == 0 and world == 1 and not args.no_rows:
+    if args.full and rank == 0 and world == 1 and not args.no_rows:
         result["rows"] = bench_rows(args, dev)
         result["live"] = bench_live(args, dev)
         result["cohort"] = bench_cohort(args, dev)
-    result["cpu_baseline"] = cpu_baseline(args) if rank == 0 and not args.no_cpu_baseline else None
+    if args.full:
+        result["cpu_baseline"] = cpu_baseline(args) if rank == 0 and not args.no_cpu_baseline else None
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:

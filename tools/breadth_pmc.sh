@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1
 mkdir -p $O/pmc
-ARGS="--no-cpu-baseline --no-rows --no-tick --no-shard --steps 1 --warmup 1 --breadth-steps 2"
+ARGS="--full --no-cpu-baseline --no-rows --no-tick --no-shard --steps 1 --warmup 1 --breadth-steps 2"
 cd /tmp
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE"; do

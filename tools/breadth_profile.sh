@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$1
 mkdir -p $O
-ARGS="--no-cpu-baseline --no-rows --no-tick --no-shard --steps 2 --warmup 1 --breadth-steps 5"
+ARGS="--full --no-cpu-baseline --no-rows --no-tick --no-shard --steps 2 --warmup 1 --breadth-steps 5"
 cd $R
 timeout -k 10 600 python -u bench.py $ARGS > $O/bench.json 2> $O/bench.err || { echo BENCH_FAILED; tail $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json'))['breadth']; print(json.dumps(d))"

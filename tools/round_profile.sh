@@ -16,7 +16,7 @@ if [ -z "$2" ]; then
 fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo SMOKE_FAILED; tail $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo BENCH_FAILED; tail $O/bench.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCH_FAILED; tail $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['shard']['frac'], d['store']['p99_ms'], d['tick']['p99_ms'], d['cpu_baseline']['value'])"
 HEAD="--no-cpu-baseline --no-rows --no-tick --no-shard --no-breadth --steps 20 --warmup 5"
 cd /tmp
