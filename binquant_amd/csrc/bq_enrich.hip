@@ -345,6 +345,73 @@ __device__ __forceinline__ void tile_arrived(bool vin, Tile& t) {
   }
 }
 
+// ---- the hot kernel's prefetch (enrich_kernel<.., HOT>) ------------------------
+// load_tile puts the vector loads and the element-wise tail loads of a field
+// on the two sides of a divergent branch; the wait-count pass follows control
+// flow, so it drains (vmcnt(0)) ahead of every field and, because the stores
+// sit behind branches too, at the loop latch. Here nothing is branched around:
+// every lane loads both of its 16-byte pairs from an in-row address (a pair
+// that would reach past T is moved back to end at T - 1, which may leave it
+// 8-byte aligned), the neighbour candle likewise, and the lanes whose candles
+// lie past T select their values where the tile is consumed
+// (tile_tail_select). Needs T >= 2 and tb >= 1; whole tiles are not altered.
+typedef dbl2 __attribute__((aligned(8))) dbl2u;
+
+__device__ __forceinline__ void load_tile_clamped(const EnrichArgs& A, int64_t row, int tb, Tile& t) {
+  const int T = A.T;
+  int64_t u[EN_K / 2];
+#pragma unroll
+  for (int j = 0; j < EN_K / 2; ++j) u[j] = row + min(tb + 2 * j, T - 2);
+  auto field = [&](const double* __restrict__ f, double (&x)[EN_K]) {
+#pragma unroll
+    for (int j = 0; j < EN_K / 2; ++j) {
+      const dbl2u a = *reinterpret_cast<const dbl2u*>(f + u[j]);
+      x[2 * j] = a.x;
+      x[2 * j + 1] = a.y;
+    }
+  };
+  field(A.in[BQ_OPEN], t.o);
+  field(A.in[BQ_HIGH], t.h);
+  field(A.in[BQ_LOW], t.l);
+  field(A.in[BQ_CLOSE], t.c);
+  field(A.in[BQ_VOLUME], t.v);
+  const int64_t n = row + min(tb - 1, T - 1);
+  t.ph = A.in[BQ_HIGH][n];
+  t.pl = A.in[BQ_LOW][n];
+  t.pc = A.in[BQ_CLOSE][n];
+}
+
+// the partial last tile as load_tile would have delivered it: candles past T
+// are 0.0, a lane whose block starts past T has no neighbour (NaN). A moved
+// pair holds candles T - 2, T - 1: candle T - 1 is its second element.
+__device__ __forceinline__ void tile_tail_select(int tb, int T, Tile& t) {
+  auto field = [&](double (&x)[EN_K]) {
+#pragma unroll
+    for (int j = 0; j < EN_K / 2; ++j) {
+      const int u = tb + 2 * j;
+      const bool both = u + 2 <= T, one = u < T;
+      x[2 * j] = both ? x[2 * j] : (one ? x[2 * j + 1] : 0.0);
+      x[2 * j + 1] = both ? x[2 * j + 1] : 0.0;
+    }
+  };
+  field(t.o);
+  field(t.h);
+  field(t.l);
+  field(t.c);
+  field(t.v);
+  if (tb > T) t.ph = t.pl = t.pc = qnan();
+}
+
+// how one instantiation of the tile body treats its tile. GEN: everything
+// decided at run time, as the generic kernels need it. The hot kernel peels
+// its tile chain instead: WARM: tile 0 (warm-up masks); RANGE: a partial tile
+// (range-checked stores); PREF: prefetches its successor (load_tile_clamped);
+// SEL: consumes a prefetched partial tile (tile_tail_select).
+template <bool GEN_, bool WARM_, bool RANGE_, bool PREF_, bool SEL_>
+struct TileMode {
+  static constexpr bool GEN = GEN_, WARM = WARM_, RANGE = RANGE_, PREF = PREF_, SEL = SEL_;
+};
+
 // VOUT: every output row 16-byte aligned (a template argument, so the
 // unaligned element-wise store path is not compiled into the common kernel)
 // DEF: the windows are the reference's (ma 7/25/100, rsi 14, bb 20, atr 14,
@@ -500,8 +567,14 @@ __device__ __forceinline__ void enrich_row_missing(const EnrichArgs& P, const Em
   }
 }
 
-template <bool DIV, bool VOUT, bool DEF>
+// HOT: the common call — all 14 outputs, inputs and outputs 16-byte aligned,
+// DEF windows, no DIV. No per-column branch is compiled, and the tile chain is
+// peeled (tile 0, whole interior tiles, partial tail) so that the loop over
+// the interior tiles has no branch around a global load or store: the waits
+// for the prefetched tile stay counted across the tile's 28 stores.
+template <bool DIV, bool VOUT, bool DEF, bool HOT = false>
 __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichArgs A, int vec_in) {
+  static_assert(!HOT || (!DIV && VOUT && DEF && !BQ_EN_LINELOAD && EN_K == 4), "HOT: the common call only");
   // LDS ring (positions [0, H) = halo from the previous tile, [H, R) = tile)
   __shared__ double sP[EN_R];    // close prefix: halo re-based, tile wave-local
   __shared__ double sC[EN_R];    // close
@@ -526,7 +599,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
   const int64_t irow = sym * A.ld_in;
   const int64_t orow = sym * A.ld_out;
   const int T = A.T;
-  const bool vin = vec_in != 0, vout = VOUT;
+  const bool vin = HOT || vec_in != 0, vout = VOUT;
 
   // the first tile's loads go out before anything else: their HBM latency
   // overlaps the serial constant set-up below (a workgroup's fixed start-up
@@ -571,16 +644,33 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     sEcar[E_SIG] = 0.0;
   }
 
-  for (int t0 = 0; t0 < T; t0 += EN_TT) {
+  const int pb = EN_H + EN_K * tid;
+  // what a tile leaves for the halo step behind it
+  int lcl[EN_K];
+  double Ploc[EN_K];
+  double y[NE];
+  // a lane's own close prefix after B1: the hot kernel reads it back from the
+  // ring (the value it wrote there) instead of holding 8 registers across the
+  // tile, which the prefetched tile needs
+  auto ploc = [&](int k) -> double {
+    if constexpr (HOT) return sP[RS1(k)];
+    else return Ploc[k];
+  };
+
+  // one tile: mode is a TileMode
+  auto tile = [&](auto mode, const int t0) {
+    using M = decltype(mode);
     const int tb = t0 + EN_K * tid;
-    const int pb = EN_H + EN_K * tid;
     const EnrichArgs& P = sA;
+    auto has = [&](int col) { return HOT || P.out[col] != nullptr; };   // HOT: every column, no branch
     Tile cu = nx;
-    tile_arrived(vin, cu);
-    if (t0 + EN_TT < T) load_tile(A, irow, tb + EN_TT, vin, nx);   // prefetch tile n+1
+    if constexpr (M::SEL) tile_tail_select(tb, T, cu);
+    else tile_arrived(vin, cu);
+    if constexpr (M::GEN) {
+      if (t0 + EN_TT < T) load_tile(A, irow, tb + EN_TT, vin, nx);   // prefetch tile n+1
+    }
 
     // ---- phase 1: per-candle quantities into the LDS ring --------------------
-    int lcl[EN_K];
     {
       bool miss = false;   // a missing / non-finite input among the lane's candles (enrich_row_missing)
       double pc = cu.pc;
@@ -605,8 +695,11 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
       }
       if (__builtin_amdgcn_ballot_w64(miss)) sMiss = 1;   // wave-uniform; read after the walk
     }
+    // the hot kernel's prefetch of tile n+1: still ahead of every store of
+    // this tile, but behind the last use of cu's open, high, low and volume,
+    // so the two tiles' registers overlap in the closes only
+    if constexpr (M::PREF) load_tile_clamped(A, irow, tb + EN_TT, nx);
     // close prefix (compensated), wave-local
-    double Ploc[EN_K];
     {
       dd tot = {0.0, 0.0};
 #pragma unroll
@@ -703,7 +796,6 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
 #pragma unroll
       for (int k = 0; k < EN_K; ++k) lcl[k] = max(lcl[k], carry);
     }
-    double y[NE];
     {
       double C[NE];
 #pragma unroll
@@ -736,11 +828,11 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
         e0[k] = y[E_0];
         e1[k] = y[E_1];
       }
-      const bool whole = t0 + EN_TT <= T;
-      if (P.out[BQ_MACD]) store4(P.out[BQ_MACD] + orow, tb, T, vout, mfast, whole);
-      if (P.out[BQ_MACD_SIGNAL]) store4(P.out[BQ_MACD_SIGNAL] + orow, tb, T, vout, msig, whole);
-      if (P.out[BQ_EMA_FAST]) store4(P.out[BQ_EMA_FAST] + orow, tb, T, vout, e0, whole);
-      if (P.out[BQ_EMA_SLOW]) store4(P.out[BQ_EMA_SLOW] + orow, tb, T, vout, e1, whole);
+      const bool whole = M::GEN ? t0 + EN_TT <= T : !M::RANGE;
+      if (has(BQ_MACD)) store4(P.out[BQ_MACD] + orow, tb, T, vout, mfast, whole);
+      if (has(BQ_MACD_SIGNAL)) store4(P.out[BQ_MACD_SIGNAL] + orow, tb, T, vout, msig, whole);
+      if (has(BQ_EMA_FAST)) store4(P.out[BQ_EMA_FAST] + orow, tb, T, vout, e0, whole);
+      if (has(BQ_EMA_SLOW)) store4(P.out[BQ_EMA_SLOW] + orow, tb, T, vout, e1, whole);
     }
 
     // ---- rolling windows -------------------------------------------------------
@@ -756,18 +848,20 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
       }
     }
     const int wstart = EN_H + EN_K * WAVE * w;   // first ring position of this wave's slice
-    // FULL: every output of the tile has a complete window (t0 >= H > max
-    // window) and the tile is complete with vector stores; drops the per-
-    // element warm-up masks and the partial-tile paths.
-    const bool full = t0 >= EN_H && t0 + EN_TT <= T && vout;
-    auto windows = [&](auto fullc) {
-      constexpr bool FULL = decltype(fullc)::value;
+    // NOWARM: every output of the tile has a complete window (t0 >= H > max
+    // window), which drops the per-element warm-up masks; FULLST: the tile is
+    // complete with vector stores, which drops the partial-tile paths. The
+    // generic kernels take both or neither, the hot kernel's peeled tiles
+    // each what holds for them.
+    auto windows = [&](auto nowarmc, auto fullstc) {
+      constexpr bool NOWARM = decltype(nowarmc)::value;   // t0 >= H: every window complete
+      constexpr bool FULLST = decltype(fullstc)::value;   // whole tile, vector stores
       const int gstart = EN_H - t0;   // ring position of candle 0 (tile 0 only)
       const int lb = pb / EN_K;
       (void)lb;
-      auto warm = [&](int t, int win) { return !FULL && t < win - 1; };
+      auto warm = [&](int t, int win) { return !NOWARM && t < win - 1; };
       auto put = [&](double* col, const double (&x)[EN_K]) {
-        if (FULL) store4(col + orow, tb, T, true, x, true);
+        if (FULLST) store4(col + orow, tb, T, true, x, true);
         else store4(col + orow, tb, T, vout, x);
       };
       // close.rolling(win).mean(): prefix difference / win, or the value
@@ -778,12 +872,12 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
         if (lcl[k] <= t - win + 1) return cu.c[k];
         const int q = p - win;
         const double base = q >= wstart ? wbw : wbp;
-        return div_exact((Ploc[k] + wbw) - (sP[RS(k - win)] + base), (double)win, inv);
+        return div_exact((ploc(k) + wbw) - (sP[RS(k - win)] + base), (double)win, inv);
       };
       double res[EN_K];
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        if (P.out[BQ_MA_FAST + i]) {
+        if (has(BQ_MA_FAST + i)) {
           const int win = win_of<DEF>(i == 0 ? 7 : (i == 1 ? 25 : 100), P.ma[i]);
           const double inv = P.inv_ma[i];
 #pragma unroll
@@ -791,7 +885,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
           put(P.out[BQ_MA_FAST + i], res);
         }
       }
-      if (P.out[BQ_BB_UPPER] || P.out[BQ_BB_MID] || P.out[BQ_BB_LOWER]) {
+      if (has(BQ_BB_UPPER) || has(BQ_BB_MID) || has(BQ_BB_LOWER)) {
         // mean from the prefix; variance from sliding sums of (c - r), (c - r)^2
         // with the lane-local reference r = close at the lane's first candle.
         double up[EN_K], mid[EN_K], lo[EN_K];
@@ -800,7 +894,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
         const bool okdv = win > P.bb_ddof;
         const double r = cu.c[0];
         double s1 = 0.0, s2 = 0.0;
-        walk_window<DEF && FULL>(FULL ? 1 - win : max(1 - win, gstart - pb), [&](int x) {
+        walk_window<DEF && NOWARM>(NOWARM ? 1 - win : max(1 - win, gstart - pb), [&](int x) {
           const double d = sC[RS(x)] - r;
           s1 += d;
           s2 = fma(d, d, s2);
@@ -810,7 +904,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
           const int t = tb + k, p = pb + k;
           if (k > 0) {
             const double dn = cu.c[k] - r;
-            const double dol = (FULL || p - win >= gstart) ? sC[RS(k - win)] - r : 0.0;
+            const double dol = (NOWARM || p - win >= gstart) ? sC[RS(k - win)] - r : 0.0;
             s1 = (s1 + dn) - dol;
             s2 = fma(-dol, dol, fma(dn, dn, s2));
           }
@@ -826,11 +920,11 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
           up[k] = m + bk * sd;
           lo[k] = m - bk * sd;
         }
-        if (P.out[BQ_BB_UPPER]) put(P.out[BQ_BB_UPPER], up);
-        if (P.out[BQ_BB_MID]) put(P.out[BQ_BB_MID], mid);
-        if (P.out[BQ_BB_LOWER]) put(P.out[BQ_BB_LOWER], lo);
+        if (has(BQ_BB_UPPER)) put(P.out[BQ_BB_UPPER], up);
+        if (has(BQ_BB_MID)) put(P.out[BQ_BB_MID], mid);
+        if (has(BQ_BB_LOWER)) put(P.out[BQ_BB_LOWER], lo);
       }
-      if (P.out[BQ_RSI]) {
+      if (has(BQ_RSI)) {
         // SMA-RSI = 100 * mean(gain) / (mean(gain) + mean(loss)) with
         // sum(gain) + sum(loss) = A = sum|d| and sum(gain) - sum(loss) = D =
         // c_t - c_{t-w} (telescoping): RSI = 50 (1 + D / A). Counts of up
@@ -860,7 +954,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
             res[k] = qnan();
             continue;
           }
-          const double D = cu.c[k] - sC[FULL ? RS(k - win) : (p - win >= gstart ? RS(k - win) : LX(gstart))];
+          const double D = cu.c[k] - sC[NOWARM ? RS(k - win) : (p - win >= gstart ? RS(k - win) : LX(gstart))];
           double v;
           if (nup == 0 && ndn == 0) v = qnan();
           else if (ndn == 0) v = 100.0;
@@ -896,15 +990,15 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
           else res[k] = div_exact(nonneg && sum < 0.0 ? 0.0 : sum, wd, inv);
         }
       };
-      if (P.out[BQ_ATR]) {
+      if (has(BQ_ATR)) {
         smean(sTR, 14, P.atr_w, P.inv_atr, true);
         put(P.out[BQ_ATR], res);
       }
-      if (P.out[BQ_TWAP]) {
+      if (has(BQ_TWAP)) {
         smean(sO4, 12, P.twap_w, P.inv_twap, false);
         put(P.out[BQ_TWAP], res);
       }
-      if (P.out[BQ_MFI]) {
+      if (has(BQ_MFI)) {
         // MFI = 100 pos / (pos + neg) with pos + neg = B = sum|f| and
         // pos - neg = F = sum f (f = signed flow): MFI = 50 (1 + F / B);
         // counts of up/down flows make the one-sided and empty windows exact.
@@ -938,30 +1032,62 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
         put(P.out[BQ_MFI], res);
       }
     };
-    if (full) windows(std::true_type{});
-    else windows(std::false_type{});
+    if constexpr (M::GEN) {
+      const bool full = t0 >= EN_H && t0 + EN_TT <= T && vout;
+      if (full) windows(std::true_type{}, std::true_type{});
+      else windows(std::false_type{}, std::false_type{});
+    } else {
+      windows(std::bool_constant<!M::WARM>{}, std::bool_constant<!M::RANGE>{});
+    }
+  };
 
-    if (t0 + EN_TT >= T) break;
+  // between two tiles: B2, then the halo for the next tile — the owners of
+  // ring positions [TT, R) copy them down, the last lane leaves the carries
+  auto halo = [&]() {
     __syncthreads();   // B2: every read of this tile's ring is done
+    // last wave, lane 63 (the copying lanes are in the last wave)
+    const double plast = HOT ? sP[LX(EN_R - 1)] : __shfl(Ploc[EN_K - 1], WAVE - 1, WAVE);
+    if (pb >= EN_TT) {
+#pragma unroll
+      for (int k = 0; k < EN_K; ++k) {
+        sP[RS1(k - EN_TT)] = ploc(k) - plast;   // re-based: halo prefix ends at 0
+        sC[RS1(k - EN_TT)] = sC[RS1(k)];
+        sTR[RS1(k - EN_TT)] = sTR[RS1(k)];
+        sO4[RS1(k - EN_TT)] = sO4[RS1(k)];
+        sMF[RS1(k - EN_TT)] = sMF[RS1(k)];
+      }
+    }
+    if (tid == EN_NT - 1) {
+#pragma unroll
+      for (int e = 0; e < NE; ++e) sEcar[e] = y[e];
+      sLcar = lcl[EN_K - 1];
+    }
+  };
 
-    // ---- halo for the next tile: owners of ring positions [TT, R) copy them --
-    {
-      const double plast = __shfl(Ploc[EN_K - 1], WAVE - 1, WAVE);   // last wave, lane 63
-      if (pb >= EN_TT) {
-#pragma unroll
-        for (int k = 0; k < EN_K; ++k) {
-          sP[RS1(k - EN_TT)] = Ploc[k] - plast;   // re-based: halo prefix ends at 0
-          sC[RS1(k - EN_TT)] = sC[RS1(k)];
-          sTR[RS1(k - EN_TT)] = sTR[RS1(k)];
-          sO4[RS1(k - EN_TT)] = sO4[RS1(k)];
-          sMF[RS1(k - EN_TT)] = sMF[RS1(k)];
-        }
-      }
-      if (tid == EN_NT - 1) {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) sEcar[e] = y[e];
-        sLcar = lcl[EN_K - 1];
-      }
+  if constexpr (!HOT) {
+    for (int t0 = 0; t0 < T; t0 += EN_TT) {
+      tile(TileMode<true, false, false, false, false>{}, t0);
+      if (t0 + EN_TT >= T) break;
+      halo();
+    }
+  } else if (T < EN_TT) {   // the only tile, partial
+    tile(TileMode<false, true, true, false, false>{}, 0);
+  } else {
+    // tile 0, then the whole interior tiles, then the partial tail: every
+    // whole tile issues its prefetch first and its 28 stores unconditionally
+    // after it, so the wait for the prefetched registers at the top of the
+    // next tile is a counted one (vmcnt(N), N >= 28) on either way into the
+    // loop. The last whole tile's prefetch is the tail's (or, without a tail,
+    // a re-read of the row's end that nothing consumes).
+    tile(TileMode<false, true, false, true, false>{}, 0);
+    int t0 = EN_TT;
+    for (; t0 + EN_TT <= T; t0 += EN_TT) {
+      halo();
+      tile(TileMode<false, false, false, true, false>{}, t0);
+    }
+    if (t0 < T) {
+      halo();
+      tile(TileMode<false, false, true, false, true>{}, t0);
     }
   }
   __syncthreads();   // sMiss final; orders the walk's stores before a rewrite's
@@ -1098,8 +1224,14 @@ int bq_enrich(const double* const* in, int64_t S, int64_t T, int64_t ld_in, cons
   hipStream_t st = (hipStream_t)stream;
   const bool def = P.ma_periods[0] == 7 && P.ma_periods[1] == 25 && P.ma_periods[2] == 100 && P.rsi_window == 14 &&
                    P.bb_window == 20 && P.atr_window == 14 && P.twap_window == 12 && P.mfi_window == 14;
+  // the common call: every column, aligned rows, the reference's windows, integer spans
+  bool hot = def && !div && vout && vin && !BQ_EN_LINELOAD && EN_K == 4;
+  for (int i = 0; i < BQ_NUM_ENRICH_COLS; ++i) hot &= out[i] != nullptr;
 #define BQ_EN_LAUNCH(D, V, F) hipLaunchKernelGGL((enrich_kernel<D, V, F>), grid, block, 0, st, A, vin)
-  if (def) {
+  if (hot) {
+    if constexpr (!BQ_EN_LINELOAD && EN_K == 4)
+      hipLaunchKernelGGL((enrich_kernel<false, true, true, true>), grid, block, 0, st, A, vin);
+  } else if (def) {
     if (div && vout) BQ_EN_LAUNCH(true, true, true);
     else if (div) BQ_EN_LAUNCH(true, false, true);
     else if (vout) BQ_EN_LAUNCH(false, true, true);
