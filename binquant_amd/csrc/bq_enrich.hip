@@ -196,16 +196,35 @@ __device__ __forceinline__ void pow_apply(const Pow& A, const double (&v)[NE], d
 // weighted /= old_wt + new_wt; skipped when weighted == cur. For every integer
 // span old_wt + new_wt == 1.0 exactly and the divide is the identity: DIV=false
 // compiles it out (the host checks this with the same IEEE arithmetic).
-template <bool DIV>
+// SEL (the hot kernel): the update is formed for every lane and selected, so
+// no branch stands around the constants' LDS reads; the generic kernels keep
+// the branch, which costs them fewer registers.
+template <bool DIV, bool SEL = false>
 __device__ __forceinline__ double ema_step(double y, double x, const EmaConsts& E, int e) {
-  if (y != x) {
-    y = E.om[e] * y + E.al[e] * x;
-    if (DIV) y = y / E.den[e];
+  static_assert(!(DIV && SEL), "SEL: without the divide only");
+  if constexpr (SEL) {
+    const double n = E.om[e] * y + E.al[e] * x;
+    return y != x ? n : y;
+  } else {
+    if (y != x) {
+      y = E.om[e] * y + E.al[e] * x;
+      if (DIV) y = y / E.den[e];
+    }
+    return y;
   }
-  return y;
 }
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+// c ? a : b on the two halves. A select whose operand is a one-use fp64
+// operation is turned back into a branch late in code generation (the operand
+// and the LDS reads feeding it sink into the branch); selects of the halves
+// stay two v_cndmask.
+__device__ __forceinline__ double sel_f64(bool c, double a, double b) {
+  const int hi = c ? __double2hiint(a) : __double2hiint(b);
+  const int lo = c ? __double2loint(a) : __double2loint(b);
+  return __hiloint2double(hi, lo);
+}
 
 __device__ __forceinline__ void load4(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[EN_K]) {
   if (vec && tb + EN_K <= T) {
@@ -590,7 +609,10 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
   __shared__ EnrichArgs sA;   // window sizes / output table, re-read from LDS each
                               // tile so the compiler cannot hoist them into registers
 
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+  // the wave index in an SGPR: the cross-wave carry steps below branch on it
+  // with scalar compares instead of looping under an exec mask
+  const int w = __builtin_amdgcn_readfirstlane(tid / WAVE);
   // Concurrently resident workgroups take scattered symbols: row streams of
   // neighbouring symbols (one HBM row pitch apart) otherwise pile onto the
   // same channels in lockstep (tools/row_ceiling.hip: +9% on the pure
@@ -657,6 +679,18 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     else return Ploc[k];
   };
 
+  // The EMA carry into a tile. The generic kernels keep it in sEcar, written
+  // in the halo step from the last lane's registers. The hot kernel writes it
+  // right after the EMA replay, while other waves may still be reading this
+  // tile's carry, so it alternates between two buffers: sEcar and the last
+  // wave's slot of sWe. A buffer written in tile n (between B1 and B2) was
+  // last read in tile n - 1 (before its B2) and is next read in tile n + 1
+  // (behind its B1).
+  constexpr bool DBUF = HOT;
+  int par = 0;   // wave-uniform: tiles done & 1
+  auto ecar_in = [&]() -> const double* { return DBUF && par ? sWe[EN_NW - 1] : sEcar; };
+  auto ecar_out = [&]() -> double* { return par ? sEcar : sWe[EN_NW - 1]; };
+
   // one tile: mode is a TileMode
   auto tile = [&](auto mode, const int t0) {
     using M = decltype(mode);
@@ -697,7 +731,9 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     }
     // the hot kernel's prefetch of tile n+1: still ahead of every store of
     // this tile, but behind the last use of cu's open, high, low and volume,
-    // so the two tiles' registers overlap in the closes only
+    // so the two tiles' registers overlap in the closes only (issued at the
+    // top of the tile, or behind the wave scans just ahead of B1, it measured
+    // 0.5-0.9 ms slower at the headline)
     if constexpr (M::PREF) load_tile_clamped(A, irow, tb + EN_TT, nx);
     // close prefix (compensated), wave-local
     {
@@ -755,17 +791,21 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
         pow_apply(E.wstep[4], c2, r);
 #pragma unroll
         for (int e = 0; e < NE; ++e) c3[e] = r[e] + readlane_f64(b[e], 47);
+        // every lane applies its power; row 0 keeps b (a select, no branch)
         const int row = lane >> 4;
-        if (row > 0) {
-          double c[NE];
+        double c[NE];
 #pragma unroll
-          for (int e = 0; e < NE; ++e) c[e] = row == 1 ? c1[e] : (row == 2 ? c2[e] : c3[e]);
-          pow_apply(E.lane[(lane & 15) + 1], c, r);
-#pragma unroll
-          for (int e = 0; e < NE; ++e) b[e] += r[e];
+        for (int e = 0; e < NE; ++e) {
+          const double a1 = c1[e], a2 = c2[e], a3 = c3[e];
+          c[e] = row == 1 ? a1 : (row == 2 ? a2 : a3);
         }
+        pow_apply(E.lane[(lane & 15) + 1], c, r);
+#pragma unroll
+        for (int e = 0; e < NE; ++e) b[e] = sel_f64(row > 0, b[e] + r[e], b[e]);
       }
-      if (lane == WAVE - 1) {
+      // (the last wave's total is read by nobody: the hot kernel keeps its
+      // second EMA carry buffer in that slot)
+      if (lane == WAVE - 1 && (!DBUF || w < EN_NW - 1)) {
 #pragma unroll
         for (int e = 0; e < NE; ++e) sWe[w][e] = b[e];
       }
@@ -781,30 +821,45 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     __syncthreads();   // B1: ring, wave totals, carries visible
 
     // ---- phase 2: carries --------------------------------------------------------
-    double wb[EN_NW];   // close-prefix base of each wave's tile slice
+    // close-prefix base of this wave's tile slice and of the slice before it
+    // (window starts are at most BQ_MAX_WINDOW < 128 candles back: this
+    // wave's slice, the previous wave's, or (wave 0) the halo, whose prefix is
+    // already based at 0). The wave index is scalar, so only the two bases
+    // stay live, not every wave's.
+    double wbw = 0.0, wbp = 0.0;
     {
       dd acc = {0.0, 0.0};
 #pragma unroll
       for (int u = 0; u < EN_NW; ++u) {
-        wb[u] = dd_round(acc);
-        acc = dd_add(acc, dd{sWh[u], sWl[u]});
+        const double base = dd_round(acc);
+        wbw = u == w ? base : wbw;
+        wbp = u + 1 == w ? base : wbp;
+        if (u + 1 < EN_NW) acc = dd_add(acc, dd{sWh[u], sWl[u]});
       }
     }
     {
       int carry = max(sLcar, lpre);
-      for (int u = 0; u < w; ++u) carry = max(carry, sWlc[u]);
+      int wl[EN_NW - 1];
+#pragma unroll
+      for (int u = 0; u < EN_NW - 1; ++u) wl[u] = sWlc[u];
+#pragma unroll
+      for (int u = 0; u < EN_NW - 1; ++u) carry = u < w ? max(carry, wl[u]) : carry;
 #pragma unroll
       for (int k = 0; k < EN_K; ++k) lcl[k] = max(lcl[k], carry);
     }
     {
       double C[NE];
 #pragma unroll
-      for (int e = 0; e < NE; ++e) C[e] = sEcar[e];
-      for (int u = 0; u < w; ++u) {
-        double r[NE];
-        pow_apply(E.wave[1], C, r);
+      for (int e = 0; e < NE; ++e) C[e] = ecar_in()[e];
+      const Pow W1 = E.wave[1];   // read once, not once per step
 #pragma unroll
-        for (int e = 0; e < NE; ++e) C[e] = r[e] + sWe[u][e];
+      for (int u = 0; u < EN_NW - 1; ++u) {
+        if (u < w) {   // a scalar compare: no exec mask around the step's LDS reads
+          double r[NE];
+          pow_apply(W1, C, r);
+#pragma unroll
+          for (int e = 0; e < NE; ++e) C[e] = r[e] + sWe[u][e];
+        }
       }
       double r[NE];
       pow_apply(E.lane[lane], C, r);
@@ -818,15 +873,24 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
 #pragma unroll
       for (int k = 0; k < EN_K; ++k) {
         const double x = cu.c[k];
-        y[E_FAST] = ema_step<DIV>(y[E_FAST], x, E, E_FAST);
-        y[E_SLOW] = ema_step<DIV>(y[E_SLOW], x, E, E_SLOW);
-        y[E_SIG] = ema_step<DIV>(y[E_SIG], y[E_FAST] - y[E_SLOW], E, E_SIG);
-        y[E_0] = ema_step<DIV>(y[E_0], x, E, E_0);
-        y[E_1] = ema_step<DIV>(y[E_1], x, E, E_1);
+        y[E_FAST] = ema_step<DIV, HOT>(y[E_FAST], x, E, E_FAST);
+        y[E_SLOW] = ema_step<DIV, HOT>(y[E_SLOW], x, E, E_SLOW);
+        y[E_SIG] = ema_step<DIV, HOT>(y[E_SIG], y[E_FAST] - y[E_SLOW], E, E_SIG);
+        y[E_0] = ema_step<DIV, HOT>(y[E_0], x, E, E_0);
+        y[E_1] = ema_step<DIV, HOT>(y[E_1], x, E, E_1);
         mfast[k] = y[E_FAST] - y[E_SLOW];
         msig[k] = y[E_SIG];
         e0[k] = y[E_0];
         e1[k] = y[E_1];
+      }
+      // the hot kernel hands the EMA state to the next tile here, into the
+      // carry buffer this tile does not read, instead of holding its 10
+      // registers across the rolling windows for the halo step
+      if constexpr (DBUF) {
+        if (tid == EN_NT - 1) {
+#pragma unroll
+          for (int e = 0; e < NE; ++e) ecar_out()[e] = y[e];
+        }
       }
       const bool whole = M::GEN ? t0 + EN_TT <= T : !M::RANGE;
       if (has(BQ_MACD)) store4(P.out[BQ_MACD] + orow, tb, T, vout, mfast, whole);
@@ -836,17 +900,6 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     }
 
     // ---- rolling windows -------------------------------------------------------
-    // Window start positions are at most BQ_MAX_WINDOW < 128 candles back, i.e.
-    // in this wave's slice, the previous wave's slice, or (wave 0) the halo,
-    // whose prefix is already based at 0.
-    double wbw = wb[0], wbp = 0.0;
-#pragma unroll
-    for (int u = 1; u < EN_NW; ++u) {
-      if (w == u) {
-        wbw = wb[u];
-        wbp = wb[u - 1];
-      }
-    }
     const int wstart = EN_H + EN_K * WAVE * w;   // first ring position of this wave's slice
     // NOWARM: every output of the tile has a complete window (t0 >= H > max
     // window), which drops the per-element warm-up masks; FULLST: the tile is
@@ -857,7 +910,11 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
       constexpr bool NOWARM = decltype(nowarmc)::value;   // t0 >= H: every window complete
       constexpr bool FULLST = decltype(fullstc)::value;   // whole tile, vector stores
       const int gstart = EN_H - t0;   // ring position of candle 0 (tile 0 only)
-      const int lb = pb / EN_K;
+      int lb = pb / EN_K;
+      // the hot kernel forms its ring addresses anew in every tile: held
+      // across the loop, the bases of the paired reads (one VGPR per array
+      // and residue class) push the loop over its register budget
+      if constexpr (HOT) asm volatile("" : "+v"(lb));
       (void)lb;
       auto warm = [&](int t, int win) { return !NOWARM && t < win - 1; };
       auto put = [&](double* col, const double (&x)[EN_K]) {
@@ -867,12 +924,15 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
       // close.rolling(win).mean(): prefix difference / win, or the value
       // itself on a constant window (pandas same-value rule).
       auto cmean = [&](int win, double inv, int k) -> double {
+        // computed for every lane (the halo keeps RS(k - win) inside the
+        // initialised ring in tile 0 too), then selected: no branch around
+        // the ring read
         const int t = tb + k, p = pb + k;
-        if (warm(t, win)) return qnan();
-        if (lcl[k] <= t - win + 1) return cu.c[k];
         const int q = p - win;
         const double base = q >= wstart ? wbw : wbp;
-        return div_exact((ploc(k) + wbw) - (sP[RS(k - win)] + base), (double)win, inv);
+        const double m = div_exact((ploc(k) + wbw) - (sP[RS(k - win)] + base), (double)win, inv);
+        const double v = lcl[k] <= t - win + 1 ? cu.c[k] : m;
+        return warm(t, win) ? qnan() : v;
       };
       double res[EN_K];
 #pragma unroll
@@ -904,18 +964,15 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
           const int t = tb + k, p = pb + k;
           if (k > 0) {
             const double dn = cu.c[k] - r;
-            const double dol = (NOWARM || p - win >= gstart) ? sC[RS(k - win)] - r : 0.0;
+            const double cold = sC[RS(k - win)];
+            const double dol = (NOWARM || p - win >= gstart) ? cold - r : 0.0;
             s1 = (s1 + dn) - dol;
             s2 = fma(-dol, dol, fma(dn, dn, s2));
           }
           const double m = cmean(win, invw, k);
-          double sd;
-          if (warm(t, win) || !okdv) sd = qnan();
-          else if (lcl[k] <= t - win + 1) sd = 0.0;
-          else {
-            const double var = (s2 - s1 * s1 * invw) * invdv;
-            sd = sqrt_nr(var);
-          }
+          const double var = (s2 - s1 * s1 * invw) * invdv;
+          const double sdv = lcl[k] <= t - win + 1 ? 0.0 : sqrt_nr(var);
+          const double sd = (warm(t, win) || !okdv) ? qnan() : sdv;
           mid[k] = m;
           up[k] = m + bk * sd;
           lo[k] = m - bk * sd;
@@ -950,17 +1007,14 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
             nup += (d > 0.0) - (dold > 0.0);
             ndn += (d < 0.0) - (dold < 0.0);
           }
-          if (warm(t, win)) {
-            res[k] = qnan();
-            continue;
-          }
           const double D = cu.c[k] - sC[NOWARM ? RS(k - win) : (p - win >= gstart ? RS(k - win) : LX(gstart))];
-          double v;
-          if (nup == 0 && ndn == 0) v = qnan();
-          else if (ndn == 0) v = 100.0;
-          else if (nup == 0) v = 0.0;
-          else v = 50.0 * (1.0 + D / A);
-          res[k] = v;
+          // one unconditional divide (A == 0 only where a select below
+          // replaces the quotient), then selects
+          double v = 50.0 * (1.0 + D / A);
+          v = nup == 0 ? 0.0 : v;
+          v = ndn == 0 ? 100.0 : v;
+          v = (nup == 0 && ndn == 0) ? qnan() : v;
+          res[k] = warm(t, win) ? qnan() : v;
         }
         put(P.out[BQ_RSI], res);
       }
@@ -985,9 +1039,9 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
             run = q == pq ? run + 1 : 1;
             pq = q;
           }
-          if (warm(t, win)) res[k] = qnan();
-          else if (run >= win) res[k] = pq;
-          else res[k] = div_exact(nonneg && sum < 0.0 ? 0.0 : sum, wd, inv);
+          const double m = div_exact(nonneg && sum < 0.0 ? 0.0 : sum, wd, inv);
+          const double v = run >= win ? pq : m;
+          res[k] = warm(t, win) ? qnan() : v;
         }
       };
       if (has(BQ_ATR)) {
@@ -1022,12 +1076,10 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
             nup += (f > 0.0) - (fo > 0.0);
             ndn += (f < 0.0) - (fo < 0.0);
           }
-          double v;
-          if (warm(t, win) || (nup == 0 && ndn == 0)) v = qnan();
-          else if (ndn == 0) v = 100.0;
-          else if (nup == 0) v = 0.0;
-          else v = 50.0 * (1.0 + F / B);
-          res[k] = v;
+          double v = 50.0 * (1.0 + F / B);
+          v = nup == 0 ? 0.0 : v;
+          v = ndn == 0 ? 100.0 : v;
+          res[k] = (warm(t, win) || (nup == 0 && ndn == 0)) ? qnan() : v;
         }
         put(P.out[BQ_MFI], res);
       }
@@ -1048,20 +1100,34 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     // last wave, lane 63 (the copying lanes are in the last wave)
     const double plast = HOT ? sP[LX(EN_R - 1)] : __shfl(Ploc[EN_K - 1], WAVE - 1, WAVE);
     if (pb >= EN_TT) {
+      // every read ahead of the first write: one round trip to LDS, not one
+      // per element (the compiler cannot tell the two ranges apart)
+      double hp[EN_K], hc[EN_K], htr[EN_K], ho4[EN_K], hmf[EN_K];
 #pragma unroll
       for (int k = 0; k < EN_K; ++k) {
-        sP[RS1(k - EN_TT)] = ploc(k) - plast;   // re-based: halo prefix ends at 0
-        sC[RS1(k - EN_TT)] = sC[RS1(k)];
-        sTR[RS1(k - EN_TT)] = sTR[RS1(k)];
-        sO4[RS1(k - EN_TT)] = sO4[RS1(k)];
-        sMF[RS1(k - EN_TT)] = sMF[RS1(k)];
+        hp[k] = ploc(k) - plast;   // re-based: halo prefix ends at 0
+        hc[k] = sC[RS1(k)];
+        htr[k] = sTR[RS1(k)];
+        ho4[k] = sO4[RS1(k)];
+        hmf[k] = sMF[RS1(k)];
+      }
+#pragma unroll
+      for (int k = 0; k < EN_K; ++k) {
+        sP[RS1(k - EN_TT)] = hp[k];
+        sC[RS1(k - EN_TT)] = hc[k];
+        sTR[RS1(k - EN_TT)] = htr[k];
+        sO4[RS1(k - EN_TT)] = ho4[k];
+        sMF[RS1(k - EN_TT)] = hmf[k];
       }
     }
     if (tid == EN_NT - 1) {
+      if constexpr (!DBUF) {
 #pragma unroll
-      for (int e = 0; e < NE; ++e) sEcar[e] = y[e];
+        for (int e = 0; e < NE; ++e) sEcar[e] = y[e];
+      }
       sLcar = lcl[EN_K - 1];
     }
+    if constexpr (DBUF) par ^= 1;
   };
 
   if constexpr (!HOT) {

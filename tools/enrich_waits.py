@@ -13,12 +13,19 @@ gfx950's vmcnt counts loads and stores alike, in order. vmcnt(0) inside the
 loop therefore drains the tile's own output stores; a counted wait (N >= the
 stores issued after the prefetch loads) lets them fly across the iteration.
 
+Per tile loop it also reports the control flow (control_flow()): exec-mask
+regions, how many of them hold an LDS access or an LDS read, exec-mask loops
+(s_cbranch_execnz), the s_waitcnt that drain the LDS counter (lgkmcnt(0)) and
+the instruction totals by class (VALU / SALU / LDS / VMEM / wait / branch).
+An LDS read inside an exec-mask region can be neither hoisted out of it nor
+batched with its neighbours: its round trip is waited for inside the region.
+
   python tools/enrich_waits.py                 # report on stdout
   python tools/enrich_waits.py --json          # the same as one JSON document
   python tools/enrich_waits.py --source FILE   # another revision of the kernel source
 
-tests/test_enrich_waits.py asserts the hot instantiation's properties from
-analyse().
+tests/test_enrich_waits.py and tests/test_enrich_straightline.py assert the
+hot instantiation's properties from analyse().
 """
 
 from __future__ import annotations
@@ -177,6 +184,69 @@ def tile_loop(body: list[str]) -> tuple[str, list[str]] | None:
     return (best[0], best[1]) if best else None
 
 
+_SAVEEXEC = re.compile(r"^\s+s_(?:and|andn2|or|xor|orn2|nand|nor|xnor)_saveexec_b64\b")
+_EXEC_NARROW = re.compile(r"^\s+s_mov_b64 exec, s")   # a mask formed outside the loop (hoisted condition)
+_EXEC_RESTORE = re.compile(r"^\s+s_or_b64 exec, exec,")
+_LGKM0 = re.compile(r"lgkmcnt\(0\)")
+
+
+def control_flow(ls: list[str]) -> dict:
+    """exec-mask regions, exec loops, LDS waits and instruction classes of a
+    loop's instruction lines. Instructions are classed by the prefix of their
+    mnemonic (v_: VALU, ds_: LDS, global_/flat_/buffer_/scratch_: VMEM,
+    s_waitcnt and s_nop: wait, s_cbranch / s_branch: branch, any other s_:
+    SALU); only the mnemonics counted here are named.
+
+    An exec-mask region opens at an s_*_saveexec_b64 (or at an
+    `s_mov_b64 exec, <mask>`, the form a loop-invariant condition takes) and
+    closes at the next
+    `s_or_b64 exec, exec, <saved>` of its nesting level, in layout order; the
+    s_andn2_saveexec_b64 / s_or_saveexec_b64 that turns an if-part into its
+    else-part continues the region. A region holds an LDS access (read) if a ds_ (ds_read) instruction
+    lies inside it or inside a region nested in it."""
+    classes = {"VALU": 0, "SALU": 0, "LDS": 0, "VMEM": 0, "wait": 0, "branch": 0, "other": 0}
+    fp64 = 0
+    open_regions: list[list[bool]] = []   # per open region: holds an LDS [access, read]
+    regions = with_lds = with_read = 0
+    for line in ls:
+        code = line.split(";")[0]
+        op = code.split()[0] if code.split() else ""
+        if op.startswith("v_"):
+            classes["VALU"] += 1
+            fp64 += op.endswith("_f64") or "_f64_" in op
+        elif op.startswith("ds_"):
+            classes["LDS"] += 1
+            open_regions = [[True, r or op.startswith("ds_read")] for _, r in open_regions]
+        elif _VMEM.match(code):
+            classes["VMEM"] += 1
+        elif op in ("s_waitcnt", "s_nop"):
+            classes["wait"] += 1
+        elif op.startswith(("s_cbranch", "s_branch")):
+            classes["branch"] += 1
+        elif op.startswith("s_"):
+            classes["SALU"] += 1
+        else:
+            classes["other"] += 1
+        if _SAVEEXEC.match(code) or _EXEC_NARROW.match(code):
+            if op.startswith(("s_or_saveexec", "s_andn2_saveexec")) and open_regions:
+                continue   # the else-part of the open region
+            regions += 1
+            open_regions.append([False, False])
+        elif _EXEC_RESTORE.match(code) and open_regions:
+            a, r = open_regions.pop()
+            with_lds += a
+            with_read += r
+    with_lds += sum(a for a, _ in open_regions)
+    with_read += sum(r for _, r in open_regions)
+    return {"exec_regions": regions, "exec_regions_with_lds": with_lds, "exec_regions_with_lds_read": with_read,
+            "saveexec": sum(1 for x in ls if _SAVEEXEC.match(x.split(";")[0])),
+            "execz_branches": sum("s_cbranch_execz" in x.split(";")[0] for x in ls),
+            "exec_loops": sum("s_cbranch_execnz" in x.split(";")[0] for x in ls),
+            "waitcnt": sum("s_waitcnt" in x.split(";")[0] for x in ls),
+            "lgkmcnt0_waits": sum(1 for x in ls if "s_waitcnt" in x.split(";")[0] and _LGKM0.search(x.split(";")[0])),
+            "fp64_valu": fp64, "classes": classes}
+
+
 def analyse(asm: str, remarks: str = "") -> list[dict]:
     usage = resource_usage(remarks)
     out = []
@@ -236,7 +306,8 @@ def analyse(asm: str, remarks: str = "") -> list[dict]:
                             "global_stores": n_stores, "nt_stores": n_nt,
                             "barriers": sum("s_barrier" in x for x in ls),
                             "scratch_ops": sum(1 for x in ls if re.match(r"\s+scratch_", x)),
-                            "waits_between_prefetch_loads": load_span_waits, "waits": waits}
+                            "waits_between_prefetch_loads": load_span_waits, "waits": waits,
+                            "control_flow": control_flow(ls)}
         out.append(rec)
     return out
 
@@ -257,6 +328,12 @@ def render(report: list[dict]) -> str:
                     f"{tl['global_stores']} global stores ({tl['nt_stores']} nt), {tl['barriers']} barriers, "
                     f"{tl['scratch_ops']} scratch ops; vmcnt waits between the first and last global load: "
                     f"{tl['waits_between_prefetch_loads']}")
+        cf = tl["control_flow"]
+        rows.append(f"   control flow: {cf['exec_regions']} exec-mask regions ({cf['exec_regions_with_lds']} holding an LDS "
+                    f"access, {cf['exec_regions_with_lds_read']} an LDS read, {cf['saveexec']} saveexec, {cf['execz_branches']} execz branches), {cf['exec_loops']} exec loops "
+                    f"(execnz); {cf['waitcnt']} s_waitcnt, {cf['lgkmcnt0_waits']} of them lgkmcnt(0)")
+        rows.append("   instructions: " + ", ".join(f"{k} {v}" for k, v in cf["classes"].items())
+                    + f"; fp64 VALU {cf['fp64_valu']}")
         for w in tl["waits"]:
             rows.append(f"   @{w['pos']:5d}  {w['text']:<34} after {w['after'] or '-':<60} "
                         f"(+{w['loads_since']} loads, +{w['stores_since']} stores"
