@@ -30,23 +30,28 @@
 //
 // Mappings (both HBM-friendly; no lane walks memory on its own):
 //   replay (mean/sum/var/std, ewm): lane = symbol, one wave per 64 symbols.
-//     Chunks of RP_CT candles are read coalesced (RP_CT lanes cover one
-//     symbol's contiguous bytes), transposed through LDS, and the next chunk
-//     is in flight while the current one is replayed; results leave through
-//     an LDS tile as coalesced row segments. The staged chunks stay in an
-//     LDS ring covering window + shift, so the value leaving the window is
-//     an LDS read and every input byte crosses HBM once.
-//   rank (quantile/median/max/min), two kernels chosen by window and shape:
+//     Chunks of 16 (8 in the all-classes kernel) candles are read coalesced
+//     (that many lanes cover one symbol's contiguous bytes), transposed
+//     through LDS, and the next chunk is in flight while the current one is
+//     replayed; results leave through the same LDS tile as coalesced row
+//     segments. The values leaving the window are RE-STAGED: the chunk w
+//     candles back is read again (a cache hit) into a second tile, so a wave
+//     holds two tiles of LDS whatever the window.
+//   ffill: a block max-scan per row (ffill_kernel), not a replay.
+//   rank (quantile/median/max/min), three kernels chosen by window and shape:
+//     stencil (w <= 32): lane = one output; the window comes from an LDS row
+//       span and is sorted by a network in registers. Also the integer sums.
 //     tile: wave = 64 (w <= 65) or 128 consecutive outputs of one symbol; the
 //       union of their windows is sorted once per wave (bitonic, registers +
-//       lane shuffles) and each lane walks it counting its window's members
-//       up to the ranks it needs. No per-lane state along the row, so no
-//       warm-up: S * T / 64 waves at any shape.
-//     lane: lane = (symbol, segment of the row). Each lane keeps its window
-//       SORTED IN REGISTERS (W slots, +inf padding): a removal / insertion is
-//       a branch-free pass of compares and selects over the W slots. A
-//       segment first rebuilds its window from the w values before it; cheap
-//       for short windows on large panels.
+//       lane shuffles) and each lane picks its ranks from it by bit selection
+//       or a walk. No per-lane state along the row, so no warm-up:
+//       S * T / 64 waves at any shape.
+//     slide (large panels, the strategies' own (window, q)): lane = (symbol,
+//       segment of the row), or 2 / 4 lanes per window (slide_group_kernel).
+//       The window of a compile-time length stays SORTED IN REGISTERS: a
+//       removal / insertion is a branch-free pass of compares and selects
+//       over the W slots. A segment first rebuilds its window from the W - 1
+//       values before it.
 #include "bq_device.h"
 #include "bq_panel.h"
 #include "binquant_amd.h"
@@ -82,7 +87,6 @@ struct RollBatch {
 };
 
 // ---- replay kernels (lane = symbol) --------------------------------------------------
-constexpr int RP_CT = 16;
 
 // pandas roll_sum / roll_mean / roll_var state, updated value by value
 struct Moments {
@@ -179,8 +183,9 @@ struct Moments {
   }
 };
 
+// 0 = ewm, 1 = Kahan sum / mean, 2 = Welford var / std
 __host__ __device__ __forceinline__ int replay_class(int mode) {
-  return mode == BQ_ROLL_FFILL ? 3 : mode == BQ_ROLL_EWM ? 0 : mode >= BQ_ROLL_VAR ? 2 : 1;
+  return mode == BQ_ROLL_EWM ? 0 : mode >= BQ_ROLL_VAR ? 2 : 1;
 }
 
 // one lane's replay state: pandas' window recurrences (Moments) or the ewm
@@ -199,11 +204,7 @@ struct ReplayLane {
   // steady: t >= window + shift + 1 (no first candle, the leaving value is
   // always inside the row) — lets a caller drop the per-step checks
   __device__ __forceinline__ double step(const RollJob& A, bool EWM, bool welford, int t, double v_in, double v_out,
-                                         bool FFILL = false, bool steady = false) {
-    if (FFILL) {   // last observation carried forward (weighted holds it; infinities are values)
-      if (v_in == v_in) weighted = v_in;
-      return weighted;
-    }
+                                         bool steady = false) {
     // window operations: NaN and +-inf are missing (every use of v_in / v_out
     // below is under its observation flag)
     if (EWM) {   // straight-line, as Moments (selects, the same values)
@@ -227,104 +228,33 @@ struct ReplayLane {
   }
 };
 
-// LDS: a ring of the last `ring` input chunks (RL = ring * RP_CT candles per
-// lane, lane-interleaved); the ring covers window + shift, so the leaving
-// value is an LDS read and every input byte crosses HBM once. Results go
-// straight from each lane to its row (consecutive steps fill a cache line
-// in L2 before it is written back).
-__global__ __launch_bounds__(WAVE) void replay_kernel(const RollBatch B, int ring) {
-  const RollJob& A = B.j[blockIdx.y];   // wave-uniform: scalar kernarg loads
-  const bool FFILL = A.mode == BQ_ROLL_FFILL;
-  const bool EWM = A.mode == BQ_ROLL_EWM || FFILL;   // no leaving value
-  extern __shared__ double smem[];
-  constexpr int TILE = RP_CT * STG_PITCH;
-  const int RL = ring * RP_CT;
-  const int lane = threadIdx.x;
-  const int64_t sym0 = (int64_t)blockIdx.x * WAVE;
-  const int64_t S = A.rows;
-  if (sym0 >= S) return;   // the block is one wave: a uniform exit
-  const int T = B.T, w = A.win, sh = A.shift;
-  const bool welford = A.mode >= BQ_ROLL_VAR;
-  const bool live = sym0 + lane < S;
-  double* __restrict__ orow = A.out + (live ? sym0 + lane : 0) * A.ld_out;
-  // ring positions of the entering (t - sh) and leaving (t - sh - w) values,
-  // advanced by one per step (no division in the loop)
-  auto wrap = [&](int i) { return ((i % RL) + RL) % RL; };
-  int pin = wrap(-sh), pout = wrap(-sh - w);
-  double ri[RP_CT];
-  stage_load<RP_CT>(A.x, A.ld_in, sym0, S, 0, T, lane, ri);
-  ReplayLane st;
-  st.init();
-  for (int t0 = 0; t0 < T; t0 += RP_CT) {
-    stage_put<RP_CT>(smem + ((t0 / RP_CT) % ring) * TILE, lane, ri);
-    __syncthreads();
-    if (t0 + RP_CT < T)   // next chunk in flight during this one's replay
-      stage_load<RP_CT>(A.x, A.ld_in, sym0, S, t0 + RP_CT, T, lane, ri);
-    auto step = [&](int j) {
-      const int t = t0 + j;
-      const double v_in = t - sh < 0 ? qnan() : smem[pin * STG_PITCH + lane];
-      const double v_out = EWM ? 0.0 : smem[pout * STG_PITCH + lane];
-      pin = pin + 1 == RL ? 0 : pin + 1;
-      pout = pout + 1 == RL ? 0 : pout + 1;
-      const double res = st.step(A, EWM, welford, t, v_in, v_out, FFILL);
-      if (live) orow[t] = res;
-    };
-    if (t0 + RP_CT <= T) {
-      // full chunk: unrolled, so each step's result / LDS traffic overlaps
-      // the next step's (short) dependent state update
-#pragma unroll
-      for (int j = 0; j < RP_CT; ++j) step(j);
-    } else {
-      for (int j = 0; j < T - t0; ++j) step(j);
-    }
-    __syncthreads();   // the ring slot of this chunk is reused RL candles later
-  }
-}
-
-// Same replay with a fixed 2-tile LDS footprint (≈17 KB per wave instead of
-// the ring's ceil((w + shift) / 16) + 1 tiles, up to 59 KB at w = 80): the
-// leaving values are staged from the input again (chunk t0 - shift - w, an
-// L2 / MALL hit: it was read w candles earlier), so up to 9 waves per CU fit
-// instead of 2-6. Costs one more read of the input (from cache).
-// CLS: 0 = ewm, 1 = Kahan sum / mean, 2 = Welford var / std, 3 = ffill — the
-// body is specialised per class (shorter dependent chain per step, and a
-// per-class launch keeps the registers to that class's state).
-// SPW: symbols per wave (64; 32, 16, 8 for measurement). With SPW < 64 the
-// same rows spread over 64/SPW times as many waves (lanes >= SPW only help
-// stage; each chunk is RS_V * 64 / SPW candles long). Measured: no faster —
-// a 12.5k-symbol replay (196 waves) costs ~600 cycles per step in the wave's
-// own ~100-instruction stream (NaN guards, the same-value rule, the IEEE
-// divide of the mean), not in a shortage of waves.
+// The replay with a fixed 2-tile LDS footprint (≈17 KB per wave): the leaving
+// values are staged from the input again (chunk t0 - shift - w, an L2 / MALL
+// hit: it was read w candles earlier), so up to 9 waves per CU fit. Costs one
+// more read of the input (from cache).
+// CLS: 0 = ewm, 1 = Kahan sum / mean, 2 = Welford var / std — the body is
+// specialised per class (shorter dependent chain per step, and a per-class
+// launch keeps the registers to that class's state).
+// A wave replays 64 symbols. A 12.5k-symbol replay (196 waves) costs ~600
+// cycles per step in the wave's own ~100-instruction stream (NaN guards, the
+// same-value rule, the IEEE divide of the mean), not in a shortage of waves.
 // staged values per lane and chunk: 16 for the class kernels, 8 for the
 // all-classes kernel (its register footprint then allows 2 waves per SIMD
-// instead of 1; measured an A/B harness of rounds 1-2 (tools/pipe_ab.sh, removed in round 3: git history): failed-spike replay 3.6 -> 3.2 ms,
-// while the class kernels are faster with 16)
-#ifndef BQ_RS_V
-#define BQ_RS_V 16
-#endif
-#ifndef BQ_RS_V_MIXED
-#define BQ_RS_V_MIXED 8
-#endif
-#ifndef BQ_RS_STAGE_OUT
-#define BQ_RS_STAGE_OUT 1   // results leave through LDS as coalesced row segments
-#endif
-#ifndef BQ_RS_WPS
-#define BQ_RS_WPS 1   // min waves per SIMD (register cap) of the re-staging replays: 1 wave, no spill (see
-                      // launch_restage: ~1 wave per SIMD at panel sizes; 2 spilled 26 VGPRs of the Welford class)
-#endif
-#ifndef BQ_RS_LPT
-#define BQ_RS_LPT 1   // mixed replay batches ordered longest class first
-#endif
-#ifndef BQ_RS_WPS_MIXED
-#define BQ_RS_WPS_MIXED 2   // the all-classes kernel
-#endif
+// instead of 1; measured: failed-spike replay 3.6 -> 3.2 ms, while the class
+// kernels are faster with 16)
+constexpr int BQ_RS_V = 16;
+constexpr int BQ_RS_V_MIXED = 8;
+// min waves per SIMD (register cap) of the class kernels: 1 wave, no spill
+// (~1 wave per SIMD at panel sizes; 2 spilled 26 VGPRs of the Welford class)
+constexpr int BQ_RS_WPS = 1;
+constexpr int BQ_RS_WPS_MIXED = 2;   // the all-classes kernel
 
-template <int SPW, int RS_V>
+template <int RS_V>
 struct ReplayTile {
-  static constexpr int CT = RS_V * WAVE / SPW;   // candles per chunk
-  static constexpr int P = SPW + 2;           // LDS pitch (doubles) of one candle's row
+  static constexpr int CT = RS_V;       // candles per chunk
+  static constexpr int P = WAVE + 2;    // LDS pitch (doubles) of one candle's row
   static constexpr int N = CT * P;
-  // [SPW symbols][CT candles] of rows sym0.. from column t0, read so that
+  // [64 symbols][CT candles] of rows sym0.. from column t0, read so that
   // consecutive lanes read consecutive candles of one row
   __device__ __forceinline__ static void load(const double* __restrict__ base, int64_t ld, int64_t sym0, int64_t S,
                                               int t0, int T, int lane, double (&r)[RS_V]) {
@@ -341,11 +271,10 @@ struct ReplayTile {
       r[k] = (s < S && t >= 0 && t < T) ? v : qnan();
     }
   }
-  // interior chunk (rows sym0 .. sym0 + SPW - 1 all < S, candles t .. t + CT - 1
+  // interior chunk (rows sym0 .. sym0 + 63 all < S, candles t .. t + CT - 1
   // all inside the row): buffer loads at a per-lane offset fixed for the whole
   // walk plus a per-k scalar row step — no per-element address arithmetic or
   // range selects (the general form above handles the edges)
-  static constexpr bool FAST = CT <= WAVE;
   __device__ __forceinline__ static void load_fast(__amdgpu_buffer_rsrc_t rs, unsigned loff, unsigned rowstep,
                                                    int t, double (&r)[RS_V]) {
     const unsigned v = loff + (unsigned)t * (unsigned)sizeof(double);
@@ -363,49 +292,46 @@ struct ReplayTile {
   }
 };
 
-// Results leave through one buffer store per step, issued by every lane:
-// rows past S and lanes >= SPW get an offset past the descriptor's range,
-// which the hardware drops. Unconditional stores keep the loop's waits
-// counted (vmcnt(N) for the prefetched chunk) instead of draining every
-// outstanding result store at each chunk boundary (gfx950's vmcnt counts
-// loads and stores alike). Host guarantees 64 * ld_out * 8 < 2^31 (job_ok).
-template <int CLS, int SPW, int RS_V>
+// Results leave through buffer stores issued by every lane (one per step in
+// the tail chunk, a chunk at a time before it): rows past S get an offset
+// past the descriptor's range, which the hardware drops. Unconditional stores
+// keep the loop's waits counted (vmcnt(N) for the prefetched chunk) instead
+// of draining every outstanding result store at each chunk boundary (gfx950's
+// vmcnt counts loads and stores alike). Host guarantees 64 * ld_out * 8 < 2^31 (job_ok).
+template <int CLS, int RS_V>
 __device__ __forceinline__ void replay_restage_body(const RollJob& A, const RollBatch& B, double* s_in,
                                                     double* s_out) {
-  using Tl = ReplayTile<SPW, RS_V>;
+  using Tl = ReplayTile<RS_V>;
   constexpr int CT = Tl::CT;
-  constexpr bool FFILL = CLS == 3;
-  constexpr bool EWM = CLS == 0 || FFILL;   // no leaving value
+  constexpr bool EWM = CLS == 0;   // no leaving value
   constexpr bool welford = CLS == 2;
   const int lane = threadIdx.x;
-  const int64_t sym0 = (int64_t)blockIdx.x * SPW;
+  const int64_t sym0 = (int64_t)blockIdx.x * WAVE;
   const int64_t S = A.rows;
   if (sym0 >= S) return;   // the block is one wave: a uniform exit
   const int T = B.T, w = A.win, sh = A.shift;
-  const int64_t rows = S - sym0 < SPW ? S - sym0 : SPW;
+  const int64_t rows = S - sym0 < WAVE ? S - sym0 : WAVE;
   const int nbytes = (int)(rows * A.ld_out * (int64_t)sizeof(double));
   const __amdgpu_buffer_rsrc_t orsrc =
       __builtin_amdgcn_make_buffer_rsrc(A.out + sym0 * A.ld_out, 0, nbytes, 0x00020000);
   const bool live = lane < rows;
   const unsigned obase = live ? (unsigned)(lane * A.ld_out * (int64_t)sizeof(double)) : (unsigned)nbytes;
-  const int rl = lane < SPW ? lane : SPW - 1;   // lanes >= SPW replay a copy (stores dropped)
   double ri[RS_V], ro[RS_V];
   Tl::load(A.x, A.ld_in, sym0, S, -sh, T, lane, ri);
   if (!EWM) Tl::load(A.x, A.ld_in, sym0, S, -sh - w, T, lane, ro);
   ReplayLane st;
   st.init();
   auto step = [&](int t, double v_in, double v_out, auto steady) {
-    const double res = st.step(A, EWM, welford, t, v_in, v_out, FFILL, decltype(steady)::value);
+    const double res = st.step(A, EWM, welford, t, v_in, v_out, decltype(steady)::value);
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(bq_u32x2, res), orsrc,
                                           obase + (unsigned)t * (unsigned)sizeof(double), 0, 0);
   };
-  // full chunks (CT <= 64): a step's result goes into the LDS slot its input
+  // full chunks: a step's result goes into the LDS slot its input
   // came from (already read by this lane), and the chunk leaves through
   // coalesced row segments after its last step — one store instruction then
   // covers 64 / CT rows x CT candles instead of 64 rows x 1 candle
-  constexpr bool OUT_LDS = Tl::FAST && BQ_RS_STAGE_OUT;
   auto step_lds = [&](int t, int j, double v_in, double v_out, auto steady) {
-    s_in[j * Tl::P + rl] = st.step(A, EWM, welford, t, v_in, v_out, FFILL, decltype(steady)::value);
+    s_in[j * Tl::P + lane] = st.step(A, EWM, welford, t, v_in, v_out, decltype(steady)::value);
   };
   // 16 steps at a time: their LDS operands are read into registers first, so
   // no LDS latency sits between two dependent state updates
@@ -414,14 +340,11 @@ __device__ __forceinline__ void replay_restage_body(const RollJob& A, const Roll
     double vi[G], vo[G];
 #pragma unroll
     for (int k = 0; k < G; ++k) {
-      vi[k] = s_in[(g + k) * Tl::P + rl];
-      vo[k] = EWM ? 0.0 : s_out[(g + k) * Tl::P + rl];
+      vi[k] = s_in[(g + k) * Tl::P + lane];
+      vo[k] = EWM ? 0.0 : s_out[(g + k) * Tl::P + lane];
     }
 #pragma unroll
-    for (int k = 0; k < G; ++k) {
-      if (OUT_LDS) step_lds(t0 + g + k, g + k, vi[k], vo[k], steady);
-      else step(t0 + g + k, vi[k], vo[k], steady);
-    }
+    for (int k = 0; k < G; ++k) step_lds(t0 + g + k, g + k, vi[k], vo[k], steady);
   };
   // the chunk's results, transposed back out of LDS: element e = lane + 64k is
   // row e / CT, candle e % CT; rows past S fall outside the descriptor
@@ -437,14 +360,14 @@ __device__ __forceinline__ void replay_restage_body(const RollJob& A, const Roll
     }
   };
   // input rows as one buffer (interior chunks load through it)
-  const bool rows_full = rows == SPW && A.ld_in <= BQ_MAX_ROLL_LD;
+  const bool rows_full = rows == WAVE && A.ld_in <= BQ_MAX_ROLL_LD;
   const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<double*>(A.x) + sym0 * A.ld_in, 0, rows_full ? (int)(SPW * A.ld_in * (int64_t)sizeof(double)) : 0,
+      const_cast<double*>(A.x) + sym0 * A.ld_in, 0, rows_full ? (int)(WAVE * A.ld_in * (int64_t)sizeof(double)) : 0,
       0x00020000);
   const unsigned loff = (unsigned)(((lane / CT) * A.ld_in + lane % CT) * (int64_t)sizeof(double));
   const unsigned rowstep = (unsigned)((WAVE / CT) * A.ld_in * (int64_t)sizeof(double));
   auto stage = [&](int t, double (&r)[RS_V]) {
-    if (Tl::FAST && rows_full && t >= 0 && t + CT <= T) Tl::load_fast(irsrc, loff, rowstep, t, r);
+    if (rows_full && t >= 0 && t + CT <= T) Tl::load_fast(irsrc, loff, rowstep, t, r);
     else Tl::load(A.x, A.ld_in, sym0, S, t, T, lane, r);
   };
   const int tfull = T - T % CT;
@@ -463,10 +386,8 @@ __device__ __forceinline__ void replay_restage_body(const RollJob& A, const Roll
 #pragma unroll 1
       for (int g = 0; g < CT; g += G) steps16(t0, g, std::false_type{});
     }
-    if (OUT_LDS) {
-      __syncthreads();   // the chunk's results are in s_in
-      flush(t0);
-    }
+    __syncthreads();   // the chunk's results are in s_in
+    flush(t0);
     __syncthreads();   // both tiles are rewritten by the next chunk
   }
   if (t0 < T) {   // tail chunk
@@ -474,35 +395,33 @@ __device__ __forceinline__ void replay_restage_body(const RollJob& A, const Roll
     if (!EWM) Tl::put(s_out, lane, ro);
     __syncthreads();
     for (int j = 0; j < T - t0; ++j)
-      step(t0 + j, s_in[j * Tl::P + rl], EWM ? 0.0 : s_out[j * Tl::P + rl], std::false_type{});
+      step(t0 + j, s_in[j * Tl::P + lane], EWM ? 0.0 : s_out[j * Tl::P + lane], std::false_type{});
   }
 }
 
 // every job of the batch is of class CLS
 // (the job is copied out of the kernel arguments once: read through a
 // reference, its fields are re-loaded from memory at every step)
-template <int CLS, int SPW>
+template <int CLS>
 __global__ __launch_bounds__(WAVE, BQ_RS_WPS) void replay_restage_kernel(const RollBatch B) {
-  __shared__ double s_in[ReplayTile<SPW, BQ_RS_V>::N];
-  __shared__ double s_out[ReplayTile<SPW, BQ_RS_V>::N];
+  __shared__ double s_in[ReplayTile<BQ_RS_V>::N];
+  __shared__ double s_out[ReplayTile<BQ_RS_V>::N];
   const RollJob A = B.j[blockIdx.y];
-  replay_restage_body<CLS, SPW, BQ_RS_V>(A, B, s_in, s_out);
+  replay_restage_body<CLS, BQ_RS_V>(A, B, s_in, s_out);
 }
 
 // jobs of any class in one launch (wave-uniform switch on the job's class):
 // for batches that do not fill the chip, where per-class launches would run
 // one latency-bound replay after the other
-template <int SPW>
 __global__ __launch_bounds__(WAVE, BQ_RS_WPS_MIXED) void replay_mixed_kernel(const RollBatch B) {
-  constexpr int V = SPW >= 16 ? BQ_RS_V_MIXED : BQ_RS_V;   // chunks of >= 8 candles for SPW < 16
-  __shared__ double s_in[ReplayTile<SPW, V>::N];
-  __shared__ double s_out[ReplayTile<SPW, V>::N];
+  constexpr int V = BQ_RS_V_MIXED;
+  __shared__ double s_in[ReplayTile<V>::N];
+  __shared__ double s_out[ReplayTile<V>::N];
   const RollJob A = B.j[blockIdx.y];
   switch (replay_class(A.mode)) {
-    case 0: replay_restage_body<0, SPW, V>(A, B, s_in, s_out); break;
-    case 1: replay_restage_body<1, SPW, V>(A, B, s_in, s_out); break;
-    case 2: replay_restage_body<2, SPW, V>(A, B, s_in, s_out); break;
-    default: replay_restage_body<3, SPW, V>(A, B, s_in, s_out);
+    case 0: replay_restage_body<0, V>(A, B, s_in, s_out); break;
+    case 1: replay_restage_body<1, V>(A, B, s_in, s_out); break;
+    default: replay_restage_body<2, V>(A, B, s_in, s_out);
   }
 }
 
@@ -554,103 +473,6 @@ __global__ __launch_bounds__(FF_NT) void ffill_kernel(const RollBatch B, int vec
     store_lines<FF_K>(out, tb, T, vec != 0, o);
     __syncthreads();   // every read of sv / sW / sCar of this tile is done
     if (tid == FF_NT - 1) sCar = cur;
-  }
-}
-
-// ---- rank kernels (lane = symbol x segment, sorted window in registers) -----------
-template <int W>
-struct SortedWin {
-  double a[W];
-  int n;
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int i = 0; i < W; ++i) a[i] = __builtin_inf();
-    n = 0;
-  }
-  // number of stored values < v (padding is +inf, never counted for finite v)
-  __device__ __forceinline__ int rank(double v) const {
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < W; ++i) p += a[i] < v ? 1 : 0;
-    return p;
-  }
-  __device__ __forceinline__ void insert(double v) {
-    const int p = rank(v);
-#pragma unroll
-    for (int i = W - 1; i > 0; --i) a[i] = i > p ? a[i - 1] : (i == p ? v : a[i]);
-    a[0] = p == 0 ? v : a[0];
-    ++n;
-  }
-  __device__ __forceinline__ void erase(double v) {   // v is stored
-    const int p = rank(v);
-#pragma unroll
-    for (int i = 0; i < W - 1; ++i) a[i] = i >= p ? a[i + 1] : a[i];
-    a[W - 1] = __builtin_inf();
-    --n;
-  }
-  // a[k] for a run-time k: a masked OR over the slots (a select chain here is
-  // folded by the compiler into one dynamically indexed load, which would
-  // push the whole window out of registers into scratch)
-  __device__ __forceinline__ double get(int k) const {
-    unsigned long long r = 0;
-#pragma unroll
-    for (int i = 0; i < W; ++i) {
-      const unsigned long long m = 0ull - (unsigned long long)(i == k);
-      r |= m & (unsigned long long)__double_as_longlong(a[i]);
-    }
-    return __longlong_as_double((long long)r);
-  }
-};
-
-template <int W>
-__global__ __launch_bounds__(256) void rank_kernel(const RollBatch B) {
-  const RollJob& A = B.j[blockIdx.y];
-  const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  // consecutive lanes: consecutive symbols of one segment
-  const int64_t sym = item % B.S;
-  const int seg = (int)(item / B.S);
-  if (seg >= A.nseg) return;
-  const double* __restrict__ x = A.x + sym * A.ld_in;
-  double* __restrict__ out = A.out + sym * A.ld_out;
-  const int T = B.T, w = A.win, sh = A.shift;
-  const int t_begin = seg * A.seg, t_end = min(T, t_begin + A.seg);
-  auto val = [&](int t) -> double {
-    const int i = t - sh;
-    return (i >= 0 && i < T) ? win_val(x[i]) : qnan();
-  };
-  SortedWin<W> win;
-  win.clear();
-  const int t_start = max(0, t_begin - w + 1);   // rebuild the window of t_begin
-  // values leave only once they were inserted by this lane (t - w >= t_start)
-  double nx_in = val(t_start), nx_out = qnan();
-  for (int t = t_start; t < t_end; ++t) {
-    const double vin = nx_in, vout = nx_out;
-    nx_in = val(t + 1);   // next step's values, in flight
-    nx_out = t + 1 - w >= t_start ? val(t + 1 - w) : qnan();
-    if (vout == vout) win.erase(vout);
-    if (vin == vin) win.insert(vin);
-    if (t < t_begin) continue;
-    const int n = win.n;
-    double r;
-    if (n < A.minp || n == 0) r = qnan();
-    else if (A.mode == BQ_ROLL_MEDIAN) {
-      const int h = n >> 1;
-      if (n & 1) r = win.get(h);
-      else {
-        r = (win.get(h - 1) + win.get(h)) / 2.0;
-      }
-    } else if (n == 1) {
-      r = win.a[0];
-    } else {   // roll_quantile, linear interpolation
-      const double idxf = A.q * (double)(n - 1);
-      const int idx = (int)idxf;
-      if ((double)idx == idxf || A.lower) r = win.get(idx);
-      else {
-        const double lo = win.get(idx), hi = win.get(idx + 1);
-        r = lo + (hi - lo) * (idxf - (double)idx);
-      }
-    }
-    out[t] = r;
   }
 }
 
@@ -883,9 +705,7 @@ __global__ __launch_bounds__(256) void slide_rank_kernel(const RollBatch B) {
   }
 }
 
-#ifndef BQ_SG_C
-#define BQ_SG_C 8   // steps per chunk of slide_group_kernel (4: 0.64 vs 0.61 ms at w = 80)
-#endif
+constexpr int BQ_SG_C = 8;   // steps per chunk of slide_group_kernel (4: 0.64 vs 0.61 ms at w = 80)
 
 // ---- slide rank kernel, lane groups (w >= 48) -----------------------------------------
 // slide_rank_kernel's sorted window split over G = 2 or 4 adjacent lanes:
@@ -1094,8 +914,8 @@ __global__ __launch_bounds__(256) void cross_kernel(const double* __restrict__ x
 // ranks it needs. The walk runs from the side nearer the ranks (descending
 // for q > 0.5) and stops when every lane is done. No lane carries state
 // along the row, so there is no warm-up per segment: parallelism is
-// S * ceil(T / TILE) waves whatever the shape (the lane kernel above needs
-// w warm-up steps per segment, which dominates at live shapes).
+// S * ceil(T / TILE) waves whatever the shape (the slide kernels above need
+// W - 1 warm-up steps per segment, which dominates at live shapes).
 __device__ __forceinline__ unsigned long long okey_nan_last(double x) {
   if (x != x) return ~0ull;
   if (x == 0.0) x = 0.0;   // -0.0 and +0.0 compare equal
@@ -1172,18 +992,12 @@ __device__ __forceinline__ int select_bit(const unsigned (&M)[NW], int r) {
 // r < n (the window's non-NaN count) is a number. Cost per wave: one scan of
 // N/32-word masks and two selections per output, instead of a walk of up to
 // N broadcast reads that every lane of the wave waits out. Measured at
-// 12.5k x 2k (tools/rank_ab.py, identical digests): 64-output tiles 0.74-0.92
+// 12.5k x 2k (identical digests): 64-output tiles 0.74-0.92
 // -> 0.57-0.61 ms for every q; 128-output tiles (256 slots, 8-word masks,
 // 43 KB of LDS per block) win for central ranks (median 96: 1.30 -> 0.92 ms)
 // and lose where the walk from the nearer end is short (q = 0.92, w = 80:
-// 0.73 -> 0.95), so the host picks per job (sel_tile).
-#ifndef BQ_RANK_SEL
-#define BQ_RANK_SEL 1   // 0: never select (measurement)
-#endif
-
-#ifndef BQ_TR_WPB
-#define BQ_TR_WPB 1   // waves per block of the tile rank kernel
-#endif
+// 0.73 -> 0.95), so the host picks per job (tile_group).
+constexpr int BQ_TR_WPB = 1;   // waves per block of the tile rank kernel
 // PACK (panel-mode jobs, bq_roll_job.panel = 1): the union slot rides in the
 // key's low log2(N) bits instead of a separate payload — one 64-bit key per
 // element through the sort (two cross-lane moves and two selects per element
@@ -1599,14 +1413,46 @@ bool job_ok(const bq_roll_job& j, int64_t S, int64_t T) {
          j.q <= 1.0;
 }
 
-int rank_bucket(int w) {
-  return w <= 8 ? 0 : w <= 24 ? 1 : w <= 48 ? 2 : w <= 64 ? 3 : w <= 80 ? 4 : 5;
-}
+// where a job of bq_rolling_batch runs
+enum class Route { Panel, Ffill, Stencil, Replay, Slide, Tile };
 
-template <int W>
-void launch_rank(const bq::RollBatch& B, int n, int64_t max_items, hipStream_t st) {
-  const unsigned blocks = (unsigned)((max_items + 255) / 256);
-  hipLaunchKernelGGL(bq::rank_kernel<W>, dim3(blocks, (unsigned)n), dim3(256), 0, st, B);
+// Environment switches, read once. Each reaches a production kernel (all give
+// identical outputs) and is how the tests run every kernel at small shapes;
+// an unset or unknown value means automatic selection.
+struct RollKnobs {
+  int rank_impl;        // BQ_RANK_IMPL=tile|stencil|slide forces one order-statistic kernel (a Route, -1: automatic)
+  int replay_impl;      // BQ_REPLAY_IMPL=restage|mixed: 1 = one launch per class, 2 = all classes in one (-1: automatic)
+  int slide_pair_min;   // BQ_SLIDE_PAIR_MIN: smallest window on slide_group_kernel (0: none)
+  int slide_group;      // BQ_SLIDE_GROUP: lanes per window there (2 or 4)
+  int slide_waves;      // BQ_SLIDE_WAVES: rounds of resident waves a slide batch is cut for (default 1)
+  bool rank_pack;       // BQ_RANK_PACK=0 keeps the full keys for panel-mode order statistics too
+  int tile_sel;         // BQ_TILE_SEL=1|0 forces selection / the walk for 128-output tiles (-1: automatic)
+  bool rank_slide;      // BQ_RANK_SLIDE=0 keeps large panels on the tile kernel
+};
+constexpr int BQ_SLIDE_PAIR_DEFAULT = 80;   // smallest window on slide_group_kernel (0: none)
+constexpr int BQ_SLIDE_GROUP_DEFAULT = 2;   // lanes per window there
+
+const RollKnobs& roll_knobs() {
+  static const RollKnobs knobs = [] {
+    auto is = [](const char* e, const char* v) { return e && strcmp(e, v) == 0; };
+    auto num = [](const char* e, int unset) { return e ? atoi(e) : unset; };
+    auto off = [](const char* e) { return e && e[0] == '0'; };
+    RollKnobs k;
+    const char* e = getenv("BQ_RANK_IMPL");
+    k.rank_impl = is(e, "tile") ? (int)Route::Tile : is(e, "stencil") ? (int)Route::Stencil
+                  : is(e, "slide") ? (int)Route::Slide : -1;
+    e = getenv("BQ_REPLAY_IMPL");
+    k.replay_impl = is(e, "restage") ? 1 : is(e, "mixed") ? 2 : -1;
+    k.slide_pair_min = num(getenv("BQ_SLIDE_PAIR_MIN"), BQ_SLIDE_PAIR_DEFAULT);
+    k.slide_group = num(getenv("BQ_SLIDE_GROUP"), BQ_SLIDE_GROUP_DEFAULT) == 4 ? 4 : 2;
+    const int rounds = num(getenv("BQ_SLIDE_WAVES"), 0);
+    k.slide_waves = rounds > 0 ? rounds : 1;
+    k.rank_pack = !off(getenv("BQ_RANK_PACK"));
+    k.tile_sel = num(getenv("BQ_TILE_SEL"), -1);
+    k.rank_slide = !off(getenv("BQ_RANK_SLIDE"));
+    return k;
+  }();
+  return knobs;
 }
 
 // slide kernel instantiations: (window, full-window rank K, median) of the
@@ -1619,20 +1465,7 @@ void launch_rank(const bq::RollBatch& B, int n, int64_t max_items, hipStream_t s
 struct SlideCfg {
   int w, k, med;
 };
-#ifndef BQ_SLIDE_BIG
-#define BQ_SLIDE_BIG 1   // 0: w = 80 / 96 on the tile kernel (measurement)
-#endif
-#ifndef BQ_SLIDE_PAIR_DEFAULT
-#define BQ_SLIDE_PAIR_DEFAULT 80   // smallest window on slide_group_kernel (0: none)
-#endif
-#ifndef BQ_SLIDE_GROUP_DEFAULT
-#define BQ_SLIDE_GROUP_DEFAULT 2   // lanes per window there
-#endif
-constexpr SlideCfg kSlide[] = {{19, 9, 1}, {48, 37, 0}, {60, 50, 0}
-#if BQ_SLIDE_BIG
-                               , {80, 72, 0}, {96, 76, 0}
-#endif
-};
+constexpr SlideCfg kSlide[] = {{19, 9, 1}, {48, 37, 0}, {60, 50, 0}, {80, 72, 0}, {96, 76, 0}};
 constexpr int kNSlide = (int)(sizeof(kSlide) / sizeof(kSlide[0]));
 
 int slide_variant(int w, int mode, double q) {
@@ -1648,26 +1481,11 @@ int slide_variant(int w, int mode, double q) {
   return -1;
 }
 
-// segment length of a slide job: lanes = (symbol, segment), about
-// BQ_SLIDE_WAVES waves per SIMD over 1024 SIMDs (the kernel is VALU-bound and
-// every slot update is independent, so a few waves hide its loads); each
-// segment replays W - 1 warm-up values, so segments stay >= 2 W
 // lanes per window of the slide kernel: 1, or BQ_SLIDE_GROUP (2 / 4) for
 // windows >= BQ_SLIDE_PAIR_MIN (0: never) — slide_group_kernel
-int slide_pair_min() {
-  static const int v = [] {
-    const char* e = getenv("BQ_SLIDE_PAIR_MIN");
-    return e ? atoi(e) : BQ_SLIDE_PAIR_DEFAULT;
-  }();
-  return v;
-}
 int slide_group(int w) {
-  static const int g = [] {
-    const char* e = getenv("BQ_SLIDE_GROUP");
-    const int v = e ? atoi(e) : BQ_SLIDE_GROUP_DEFAULT;
-    return v == 4 ? 4 : 2;
-  }();
-  return slide_pair_min() > 0 && w >= slide_pair_min() && w % g == 0 ? g : 1;
+  const RollKnobs& k = roll_knobs();
+  return k.slide_pair_min > 0 && w >= k.slide_pair_min && w % k.slide_group == 0 ? k.slide_group : 1;
 }
 
 // Segments of a slide batch (lanes = (symbol, segment) x G lanes per window):
@@ -1698,11 +1516,7 @@ int resident_waves(F kern) {   // 256-thread workgroups per CU = waves per SIMD
 // chunks) at 7 segments (175k lanes x 256 B > the L2) ran 0.43 ms, at 5
 // (125k lanes) 0.34.
 int64_t slide_segments(bq::RollBatch& B, int n, int w, int g, int occ, int chunk) {
-  static const int rounds = [] {
-    const char* e = getenv("BQ_SLIDE_WAVES");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 1;
-  }();
+  const int rounds = roll_knobs().slide_waves;
   const int64_t l2_items = ((int64_t)32 << 20) / (2 * chunk * 8);
   int64_t items = (int64_t)device_cus() * 4 * occ * 64 * rounds / g;
   items = items < l2_items * rounds ? items : l2_items * rounds;
@@ -1734,14 +1548,14 @@ void launch_slide1(const bq::RollBatch& B0, int n, hipStream_t st, bool single) 
     const int g = slide_group(W);
     if (g == 2) {
       static const int occ = resident_waves(bq::slide_group_kernel<W, K, MED, 2>);
-      const int64_t items = slide_segments(B, n, W, 2, occ, BQ_SG_C);
+      const int64_t items = slide_segments(B, n, W, 2, occ, bq::BQ_SG_C);
       const unsigned blocks = (unsigned)((2 * items + 255) / 256);
       hipLaunchKernelGGL((bq::slide_group_kernel<W, K, MED, 2>), dim3(blocks, (unsigned)n), dim3(256), 0, st, B);
       return;
     }
     if (g == 4) {
       static const int occ = resident_waves(bq::slide_group_kernel<W, K, MED, 4>);
-      const int64_t items = slide_segments(B, n, W, 4, occ, BQ_SG_C);
+      const int64_t items = slide_segments(B, n, W, 4, occ, bq::BQ_SG_C);
       const unsigned blocks = (unsigned)((4 * items + 255) / 256);
       hipLaunchKernelGGL((bq::slide_group_kernel<W, K, MED, 4>), dim3(blocks, (unsigned)n), dim3(256), 0, st, B);
       return;
@@ -1753,36 +1567,16 @@ void launch_slide1(const bq::RollBatch& B0, int n, hipStream_t st, bool single) 
   hipLaunchKernelGGL((bq::slide_rank_kernel<W, K, MED>), dim3(blocks, (unsigned)n), dim3(256), 0, st, B);
 }
 
-// single: the one-lane kernel with the crossing flags (bq_rolling_quantile_cross)
-void launch_slide(int v, const bq::RollBatch& B, int n, hipStream_t st, bool single = false) {
+// v: index into kSlide; single: the one-lane kernel with the crossing flags
+// (bq_rolling_quantile_cross)
+void launch_slide(int v, const bq::RollBatch& B, int n, hipStream_t st, bool single) {
   switch (v) {
     case 0: launch_slide1<19, 9, true>(B, n, st, single); break;
     case 1: launch_slide1<48, 37, false>(B, n, st, single); break;
-#if BQ_SLIDE_BIG
+    case 2: launch_slide1<60, 50, false>(B, n, st, single); break;
     case 3: launch_slide1<80, 72, false>(B, n, st, single); break;
     case 4: launch_slide1<96, 76, false>(B, n, st, single); break;
-#endif
-    default: launch_slide1<60, 50, false>(B, n, st, single);
   }
-}
-static_assert(kNSlide == 3 + 2 * BQ_SLIDE_BIG, "launch_slide covers every kSlide entry");
-
-template <int EPL, int OPL, bool SEL, bool PACK>
-void launch_tile_rank(const bq::RollBatch& B, int n, hipStream_t st) {
-  const int64_t nt = (B.T + bq::WAVE * OPL - 1) / (bq::WAVE * OPL);
-  const unsigned blocks = (unsigned)((B.S * nt + BQ_TR_WPB - 1) / BQ_TR_WPB);
-  hipLaunchKernelGGL((bq::tile_rank_kernel<EPL, OPL, SEL, PACK>), dim3(blocks, (unsigned)n), dim3(64 * BQ_TR_WPB), 0,
-                     st, B);
-}
-
-// panel-mode order statistics with packed keys (tile_rank_kernel PACK);
-// BQ_RANK_PACK=0 keeps the full keys for them too (measurement)
-bool rank_pack() {
-  static const bool on = [] {
-    const char* e = getenv("BQ_RANK_PACK");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 // tile group of a job: 0 = 64-output tiles (w <= 65: union fits 128 slots),
@@ -1790,16 +1584,32 @@ bool rank_pack() {
 // the walk where the rank is near an end of the window (tile_rank_kernel)
 int tile_group(int w, int mode, double q) {
   if (w <= 65) return 0;
-  // BQ_TILE_SEL=1|0 forces selection / the walk for 128-output tiles (measurement)
-  static const int forced = [] {
-    const char* e = getenv("BQ_TILE_SEL");
-    return e ? atoi(e) : -1;
-  }();
+  const int forced = roll_knobs().tile_sel;
   if (forced >= 0) return forced ? 1 : 2;
   // central ranks select (measured, tools/tile_sel_ab.sh: w 96 q 0.8 2.64 vs 3.27 ms
   // a call; w 80 q 0.92 2.70 vs 2.57 — the walk from the top end is short)
   const bool central = mode == BQ_ROLL_MEDIAN || (q >= 0.2 && q <= 0.8);
-  return BQ_RANK_SEL && central ? 1 : 2;
+  return central ? 1 : 2;
+}
+
+template <int EPL, int OPL, bool SEL, bool PACK>
+void launch_tile_rank(const bq::RollBatch& B, int n, hipStream_t st) {
+  const int64_t nt = (B.T + bq::WAVE * OPL - 1) / (bq::WAVE * OPL);
+  const unsigned blocks = (unsigned)((B.S * nt + bq::BQ_TR_WPB - 1) / bq::BQ_TR_WPB);
+  hipLaunchKernelGGL((bq::tile_rank_kernel<EPL, OPL, SEL, PACK>), dim3(blocks, (unsigned)n),
+                     dim3(64 * bq::BQ_TR_WPB), 0, st, B);
+}
+
+// g: tile_group, + 3 for panel-mode jobs (packed keys, tile_rank_kernel PACK)
+void launch_tile(int g, const bq::RollBatch& B, int n, hipStream_t st) {
+  switch (g) {
+    case 0: launch_tile_rank<2, 1, true, false>(B, n, st); break;
+    case 1: launch_tile_rank<4, 2, true, false>(B, n, st); break;
+    case 2: launch_tile_rank<4, 2, false, false>(B, n, st); break;
+    case 3: launch_tile_rank<2, 1, true, true>(B, n, st); break;
+    case 4: launch_tile_rank<4, 2, true, true>(B, n, st); break;
+    default: launch_tile_rank<4, 2, false, true>(B, n, st);
+  }
 }
 
 // window buckets of the stencil kernel (network slots): a bucket of 20 for
@@ -1819,99 +1629,168 @@ void launch_stencil(int b, const bq::RollBatch& B, int n, hipStream_t st) {
   }
 }
 
-// which replay kernel: 0 = LDS ring over the window (one launch, 64 symbols
-// per wave), 1 = re-staged leaving values, one launch per class, 2 = re-staged,
-// all classes in one launch. BQ_REPLAY_IMPL=ring|restage|mixed forces one
-// (measurement; all give identical outputs).
-int replay_impl(int nclasses, int64_t waves64) {
-  static const int forced = [] {
-    const char* e = getenv("BQ_REPLAY_IMPL");
-    return !e ? -1
-              : (strcmp(e, "ring") == 0      ? 0
-                 : strcmp(e, "restage") == 0 ? 1
-                 : strcmp(e, "mixed") == 0   ? 2
-                                             : -1);
-  }();
-  if (forced >= 0) return forced;
-  // mixed classes: one launch (measured, an A/B harness of rounds 1-2 (tools/replay_ab.sh, removed in round 3: git history), identical
-  // digests: 1000 x 400 batch16 0.18 vs 0.33 ms per class; 12.5k x 2k
-  // batch16 2.69 vs 2.87 ms — the classes' replays overlap instead of
-  // running one after the other)
-  (void)waves64;
-  return nclasses > 1 ? 2 : 1;
-}
-
-// symbols per wave of the re-staged replays: 64. BQ_REPLAY_SPW=32|16|8
-// forces fewer (measurement: spreading the rows over 2-4x as many waves did
-// not shorten the replay even for small batches — ADX's 3 series over 12.5k
-// symbols (588 waves of 64) took 1.12 ms at 64 and 1.49 ms at 16 symbols per
-// wave: the step cost is the wave's own instruction stream, not a shortage of
-// waves — an A/B harness of rounds 1-2 (tools/spw_ab.sh, removed in round 3: git history), an A/B harness of rounds 1-2 (tools/replay_ab.sh, removed in round 3: git history)).
-int replay_spw(int64_t waves64) {
-  static const int forced = [] {
-    const char* e = getenv("BQ_REPLAY_SPW");
-    const int v = e ? atoi(e) : 0;
-    return (v == 32 || v == 16 || v == 8) ? v : 64;
-  }();
-  (void)waves64;
-  return forced;
-}
-
-template <int SPW>
+// cls 0-2: every job of that replay class; 3: any classes (the mixed kernel)
 void launch_restage(int cls, const bq::RollBatch& B, int n, hipStream_t st) {
-  const dim3 grid((unsigned)((B.S + SPW - 1) / SPW), (unsigned)n);
+  const dim3 grid((unsigned)((B.S + bq::WAVE - 1) / bq::WAVE), (unsigned)n);
   switch (cls) {
-    case 0: hipLaunchKernelGGL((bq::replay_restage_kernel<0, SPW>), grid, dim3(bq::WAVE), 0, st, B); break;
-    case 1: hipLaunchKernelGGL((bq::replay_restage_kernel<1, SPW>), grid, dim3(bq::WAVE), 0, st, B); break;
-    case 2: hipLaunchKernelGGL((bq::replay_restage_kernel<2, SPW>), grid, dim3(bq::WAVE), 0, st, B); break;
-    case 3: hipLaunchKernelGGL((bq::replay_restage_kernel<3, SPW>), grid, dim3(bq::WAVE), 0, st, B); break;
-    default: hipLaunchKernelGGL((bq::replay_mixed_kernel<SPW>), grid, dim3(bq::WAVE), 0, st, B);
+    case 0: hipLaunchKernelGGL(bq::replay_restage_kernel<0>, grid, dim3(bq::WAVE), 0, st, B); break;
+    case 1: hipLaunchKernelGGL(bq::replay_restage_kernel<1>, grid, dim3(bq::WAVE), 0, st, B); break;
+    case 2: hipLaunchKernelGGL(bq::replay_restage_kernel<2>, grid, dim3(bq::WAVE), 0, st, B); break;
+    default: hipLaunchKernelGGL(bq::replay_mixed_kernel, grid, dim3(bq::WAVE), 0, st, B);
   }
 }
 
-// cls 0-3: one class; 4: mixed
-void launch_restage_any(int cls, const bq::RollBatch& B, int n, hipStream_t st) {
-  switch (replay_spw((B.S + bq::WAVE - 1) / bq::WAVE * n)) {
-    case 64: launch_restage<64>(cls, B, n, st); break;
-    case 32: launch_restage<32>(cls, B, n, st); break;
-    case 16: launch_restage<16>(cls, B, n, st); break;
-    default: launch_restage<8>(cls, B, n, st);
+// A replay batch: the class-specialised kernel when it has one class, the
+// mixed kernel otherwise — one launch (measured, identical digests: 1000 x 400
+// batch16 0.18 vs 0.33 ms per class; 12.5k x 2k batch16 2.69 vs 2.87 ms — the
+// classes' replays overlap instead of running one after the other).
+void launch_replay(bq::RollBatch& B, int n, hipStream_t st) {
+  int ncls[3] = {0, 0, 0};
+  for (int i = 0; i < n; ++i) ++ncls[bq::replay_class(B.j[i].mode)];
+  const int nclasses = (ncls[0] > 0) + (ncls[1] > 0) + (ncls[2] > 0);
+  const int forced = roll_knobs().replay_impl;
+  if ((forced >= 0 ? forced : nclasses > 1 ? 2 : 1) == 1) {
+    for (int c = 0; c < 3; ++c) {
+      if (!ncls[c]) continue;
+      bq::RollBatch cls = B;
+      int m = 0;
+      for (int i = 0; i < n; ++i)
+        if (bq::replay_class(B.j[i].mode) == c) cls.j[m++] = B.j[i];
+      launch_restage(c, cls, m, st);
+    }
+    return;
   }
+  // longest first: blocks start in blockIdx order (x, then the job), so the
+  // costliest replays (Welford, ~3x a Kahan step) go to the front of the grid
+  // instead of starting in its tail (outputs are per job)
+  bq::RollJob sorted[bq::RW_MAXJOBS];
+  int m = 0;
+  for (int c : {2, 1, 0})
+    for (int i = 0; i < n; ++i)
+      if (bq::replay_class(B.j[i].mode) == c) sorted[m++] = B.j[i];
+  for (int i = 0; i < n; ++i) B.j[i] = sorted[i];
+  launch_restage(3, B, n, st);
 }
 
-// which order-statistic kernel: 0 = lane (sorted window per lane), 1 = tile
-// (sorted union per wave), 2 = stencil (sorting network per output, w <= 32).
-// BQ_RANK_IMPL=lane|tile|stencil forces one (measurement; stencil falls back
-// to tile above w = 32).
-// BQ_RANK_SLIDE=0 keeps large panels on the tile kernel (measurement)
-bool slide_on() {
-  static const bool on = [] {
-    const char* e = getenv("BQ_RANK_SLIDE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+void launch_ffill(const bq::RollBatch& B, int n, hipStream_t st) {
+  int vec = 1;   // 16-byte output rows: whole-line stores
+  for (int i = 0; i < n; ++i) vec &= (B.j[i].ld_out % 2) == 0 && (((uintptr_t)B.j[i].out) & 15u) == 0;
+  hipLaunchKernelGGL(bq::ffill_kernel, dim3((unsigned)B.S, (unsigned)n), dim3(bq::FF_NT), 0, st, B, vec);
 }
 
-int rank_impl(int w, int64_t S, int64_t T, bool slide) {
-  static const int forced = [] {
-    const char* e = getenv("BQ_RANK_IMPL");
-    return !e ? -1
-              : (strcmp(e, "lane") == 0      ? 0
-                 : strcmp(e, "tile") == 0    ? 1
-                 : strcmp(e, "stencil") == 0 ? 2
-                 : strcmp(e, "slide") == 0   ? 3
-                                             : -1);
-  }();
-  if (forced == 3) return slide ? 3 : (w <= 32 ? 2 : 1);
-  if (forced >= 0) return forced == 2 && w > 32 ? 1 : forced;
+// which order-statistic kernel (Stencil, Tile or Slide) takes a window;
+// slide: the job has a slide instantiation
+Route rank_route(int w, int64_t S, int64_t T, bool slide) {
+  const RollKnobs& k = roll_knobs();
+  const Route plain = w <= 32 ? Route::Stencil : Route::Tile;
+  if (k.rank_impl == (int)Route::Slide) return slide ? Route::Slide : plain;
+  if (k.rank_impl >= 0) return k.rank_impl == (int)Route::Stencil ? plain : Route::Tile;
   // large panels with a slide instantiation: the sorted-register window
   // (5 VALU per slot and step, against the tile kernel's sort per 64
   // outputs); live shapes keep the tile / stencil kernels (no warm-up)
-  if (slide && S * T >= (int64_t)(1 << 22) && T >= 4 * (int64_t)w && slide_on()) return 3;
+  if (slide && S * T >= (int64_t)(1 << 22) && T >= 4 * (int64_t)w && k.rank_slide) return Route::Slide;
   // short windows: the stencil kernel (coalesced, no warm-up, no per-lane row
   // walk); longer ones: the tile kernel, whose sort is shared by 64 / 128
-  // outputs (the lane kernel stays selectable for measurement)
-  return w <= 32 ? 2 : 1;
+  // outputs
+  return plain;
+}
+
+struct Routed {
+  Route to;
+  int bucket;   // Stencil: stencil_bucket; Slide: index into kSlide; Tile: launch_tile's group
+  int mode;     // the kernels' mode: QLOWER runs as QUANTILE, a long-window ISUM as SUM
+};
+
+// where job `in` of an [S][T] batch goes; asked once per job
+Routed route_job(const bq_roll_job& in, int64_t S, int64_t T) {
+  if (in.panel && bq::panel_supported(in.mode, in.window, in.shift))   // time-parallel (bq_panel.hip)
+    return {Route::Panel, 0, in.mode};
+  if (in.mode == BQ_ROLL_FFILL) return {Route::Ffill, 0, in.mode};   // a scan, not a replay (ffill_kernel)
+  const bool stencil_fits = S * ((T + bq::SR_NT - 1) / bq::SR_NT) <= 0x7fffffff;   // its grid's x
+  if (in.mode == BQ_ROLL_ISUM) {
+    // integer-valued sum: a direct window sum in the stencil launch; a long
+    // window takes the replay (identical values for integer series)
+    if (in.window <= 32 && stencil_fits) return {Route::Stencil, stencil_bucket(in.window), in.mode};
+    return {Route::Replay, 0, BQ_ROLL_SUM};
+  }
+  // QLOWER: an order statistic like the quantile, no interpolation (RollJob.lower)
+  const int mode = in.mode == BQ_ROLL_QLOWER ? BQ_ROLL_QUANTILE : in.mode;
+  if (mode >= BQ_ROLL_MEAN) return {Route::Replay, 0, mode};   // moments / ewm: exact replay
+  const int sv = slide_variant(in.window, mode, in.q);
+  const Route r = rank_route(in.window, S, T, sv >= 0);
+  if (r == Route::Slide) return {r, sv, mode};
+  if (r == Route::Stencil && stencil_fits) return {r, stencil_bucket(in.window), mode};
+  return {Route::Tile, tile_group(in.window, in.mode, in.q) + (in.panel && roll_knobs().rank_pack ? 3 : 0), mode};
+}
+
+// NB batches of one kind (one per bucket) with their counts and the callable
+// that launches one: push() appends a job and launches the batch once it is
+// full, flush() launches what is queued
+template <typename Batch, int NB, typename Launch>
+struct JobQueues {
+  static constexpr int CAP = (int)(sizeof(Batch::j) / sizeof(Batch::j[0]));
+  Batch b[NB];
+  int n[NB];
+  Launch launch;   // launch(bucket, batch, count)
+  JobQueues(int64_t S, int64_t T, Launch l) : launch(l) {
+    memset(b, 0, sizeof(b));
+    memset(n, 0, sizeof(n));
+    for (Batch& x : b) {
+      x.S = S;
+      x.T = (int)T;
+    }
+  }
+  template <typename Job>
+  void push(int k, const Job& j) {
+    b[k].j[n[k]++] = j;
+    if (n[k] == CAP) flush(k);
+  }
+  void flush(int k) {
+    if (!n[k]) return;
+    launch(k, b[k], n[k]);
+    n[k] = 0;
+  }
+  void flush() {
+    for (int k = 0; k < NB; ++k) flush(k);
+  }
+};
+template <typename Batch, int NB, typename Launch>
+JobQueues<Batch, NB, Launch> job_queues(int64_t S, int64_t T, Launch l) {
+  return {S, T, l};
+}
+
+bq::PanelJob panel_job(const bq_roll_job& in, int64_t S) {
+  bq::PanelJob P;
+  P.x = in.x;
+  P.out = in.out;
+  P.ld_in = in.ld_in;
+  P.ld_out = in.ld_out;
+  P.rows = in.rows > 0 ? in.rows : S;
+  P.win = in.window;
+  P.minp = in.min_periods;
+  P.shift = in.shift;
+  P.mode = in.mode;
+  P.alpha = in.alpha;
+  P.hi = P.lo = nullptr;
+  return P;
+}
+
+bq::RollJob roll_job(const bq_roll_job& in, int64_t S, int mode) {
+  bq::RollJob J;
+  memset(&J, 0, sizeof(J));
+  J.x = in.x;
+  J.out = in.out;
+  J.ld_in = in.ld_in;
+  J.ld_out = in.ld_out;
+  J.win = in.window;
+  J.minp = in.min_periods;
+  J.shift = in.shift;
+  J.mode = mode;
+  J.lower = in.mode == BQ_ROLL_QLOWER;
+  J.q = in.q;
+  J.alpha = in.alpha;
+  J.rows = in.rows > 0 ? in.rows : S;
+  return J;
 }
 
 }  // namespace
@@ -1938,257 +1817,48 @@ int bq_rolling_batch_cross(const bq_roll_job* jobs, int32_t n_jobs, int64_t S, i
   bool slide_xc[kNSlide] = {};
   for (int i = 0; i < n_jobs; ++i)
     if (cross && cross[i]) {
-      const int sv = slide_variant(jobs[i].window, jobs[i].mode, jobs[i].q);
-      if (sv >= 0 && rank_impl(jobs[i].window, S, T, true) == 3) slide_xc[sv] = true;
+      const Routed r = route_job(jobs[i], S, T);
+      if (r.to == Route::Slide) slide_xc[r.bucket] = true;
     }
   int nxp = 0;
   int xpass[BQ_MAX_ROLL_JOBS];
-  // replay jobs (moments, ewm): lane = symbol; rank jobs grouped by window size
-  RollBatch rep;
-  memset(&rep, 0, sizeof(rep));
-  rep.S = S;
-  rep.T = (int)T;
-  int nrep = 0;
-  RollBatch rank[6];
-  int nrank[6] = {0, 0, 0, 0, 0, 0};
-  int64_t rank_items[6] = {0, 0, 0, 0, 0, 0};
-  for (int b = 0; b < 6; ++b) {
-    memset(&rank[b], 0, sizeof(RollBatch));
-    rank[b].S = S;
-    rank[b].T = (int)T;
-  }
-  int max_back = 0;   // window + shift of the replay jobs in the batch
-  auto flush_rep = [&]() {
-    if (!nrep) return;
-    const int ring = (max_back + RP_CT - 1) / RP_CT + 1;
-    const size_t lds = (size_t)ring * RP_CT * STG_PITCH * sizeof(double);
-    // > 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU): set once, before
-    // any graph capture can be active (first call of the process)
-    static const bool lds_opt_in =
-        hipFuncSetAttribute((const void*)replay_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) ==
-        hipSuccess;
-    (void)lds_opt_in;
-    // re-staging kernels: class-specialised when the batch has one class,
-    // the mixed kernel otherwise (the LDS ring kernel only when forced;
-    // measured: an A/B harness of rounds 1-2 (tools/replay_ab.sh, removed in round 3: git history), identical outputs)
-    int ncls[4] = {0, 0, 0, 0};
-    for (int i = 0; i < nrep; ++i) ++ncls[replay_class(rep.j[i].mode)];
-    const int nclasses = (ncls[0] > 0) + (ncls[1] > 0) + (ncls[2] > 0) + (ncls[3] > 0);
-    const int impl = replay_impl(nclasses, ((S + WAVE - 1) / WAVE) * nrep);
-    if (impl == 1) {
-      RollBatch cls[4];
-      for (int c = 0; c < 4; ++c) {
-        memset(&cls[c], 0, sizeof(RollBatch));
-        cls[c].S = S;
-        cls[c].T = (int)T;
-        ncls[c] = 0;
-      }
-      for (int i = 0; i < nrep; ++i) {
-        const int c = replay_class(rep.j[i].mode);
-        cls[c].j[ncls[c]++] = rep.j[i];
-      }
-      for (int c = 0; c < 4; ++c)
-        if (ncls[c]) launch_restage_any(c, cls[c], ncls[c], st);
-    } else if (impl == 2) {
-      // longest first: blocks start in blockIdx order (x, then the job), so
-      // the costliest replays (Welford, ~3x a Kahan step) go to the front of
-      // the grid instead of starting in its tail (outputs are per job)
-      if (BQ_RS_LPT) {
-        RollJob sorted[RW_MAXJOBS];
-        int n = 0;
-        for (int c : {2, 1, 0, 3})
-          for (int i = 0; i < nrep; ++i)
-            if (replay_class(rep.j[i].mode) == c) sorted[n++] = rep.j[i];
-        for (int i = 0; i < nrep; ++i) rep.j[i] = sorted[i];
-      }
-      launch_restage_any(4, rep, nrep, st);
-    } else {
-      hipLaunchKernelGGL(replay_kernel, dim3((unsigned)((S + WAVE - 1) / WAVE), (unsigned)nrep), dim3(WAVE), lds, st,
-                         rep, ring);
-    }
-    nrep = 0;
-    max_back = 0;
-  };
-  auto flush_rank = [&](int b) {
-    if (!nrank[b]) return;
-    switch (b) {
-      case 0: launch_rank<8>(rank[b], nrank[b], rank_items[b], st); break;
-      case 1: launch_rank<24>(rank[b], nrank[b], rank_items[b], st); break;
-      case 2: launch_rank<48>(rank[b], nrank[b], rank_items[b], st); break;
-      case 3: launch_rank<64>(rank[b], nrank[b], rank_items[b], st); break;
-      case 4: launch_rank<80>(rank[b], nrank[b], rank_items[b], st); break;
-      default: launch_rank<96>(rank[b], nrank[b], rank_items[b], st);
-    }
-    nrank[b] = 0;
-    rank_items[b] = 0;
-  };
-  RollBatch tile[6];   // tile group + 3 for panel-mode (packed-key) jobs
-  int ntile[6] = {0, 0, 0, 0, 0, 0};
-  for (int g = 0; g < 6; ++g) {
-    memset(&tile[g], 0, sizeof(RollBatch));
-    tile[g].S = S;
-    tile[g].T = (int)T;
-  }
-  auto flush_tile = [&](int g) {
-    if (!ntile[g]) return;
-    switch (g) {
-      case 0: launch_tile_rank<2, 1, BQ_RANK_SEL != 0, false>(tile[g], ntile[g], st); break;
-      case 1: launch_tile_rank<4, 2, true, false>(tile[g], ntile[g], st); break;
-      case 2: launch_tile_rank<4, 2, false, false>(tile[g], ntile[g], st); break;
-      case 3: launch_tile_rank<2, 1, BQ_RANK_SEL != 0, true>(tile[g], ntile[g], st); break;
-      case 4: launch_tile_rank<4, 2, true, true>(tile[g], ntile[g], st); break;
-      default: launch_tile_rank<4, 2, false, true>(tile[g], ntile[g], st);
-    }
-    ntile[g] = 0;
-  };
-  RollBatch slide[kNSlide];
-  int nslide[kNSlide] = {};
-
-  for (int v = 0; v < kNSlide; ++v) {
-    memset(&slide[v], 0, sizeof(RollBatch));
-    slide[v].S = S;
-    slide[v].T = (int)T;
-  }
-  auto flush_slide = [&](int v) {
-    if (!nslide[v]) return;
-    launch_slide(v, slide[v], nslide[v], st, slide_xc[v]);   // segments set there
-    nslide[v] = 0;
-  };
-  RollBatch ff;
-  memset(&ff, 0, sizeof(ff));
-  ff.S = S;
-  ff.T = (int)T;
-  int nff = 0;
-  auto flush_ff = [&]() {
-    if (!nff) return;
-    int vec = 1;   // 16-byte output rows: whole-line stores
-    for (int i = 0; i < nff; ++i)
-      vec &= (ff.j[i].ld_out % 2) == 0 && (((uintptr_t)ff.j[i].out) & 15u) == 0;
-    hipLaunchKernelGGL(ffill_kernel, dim3((unsigned)S, (unsigned)nff), dim3(FF_NT), 0, st, ff, vec);
-    nff = 0;
-  };
-  RollBatch sten[6];
-  int nsten[6] = {0, 0, 0, 0, 0, 0};
-  for (int b = 0; b < 6; ++b) {
-    memset(&sten[b], 0, sizeof(RollBatch));
-    sten[b].S = S;
-    sten[b].T = (int)T;
-  }
-  auto flush_sten = [&](int b) {
-    if (!nsten[b]) return;
-    launch_stencil(b, sten[b], nsten[b], st);
-    nsten[b] = 0;
-  };
-  PanelBatch pan;
-  memset(&pan, 0, sizeof(pan));
-  pan.S = S;
-  pan.T = (int)T;
-  int npan = 0;
-  auto flush_pan = [&]() {
-    if (!npan) return;
-    launch_panel(pan, npan, st);
-    npan = 0;
-  };
+  auto pan = job_queues<PanelBatch, 1>(S, T, [&](int, PanelBatch& B, int n) { launch_panel(B, n, st); });
+  auto rep = job_queues<RollBatch, 1>(S, T, [&](int, RollBatch& B, int n) { launch_replay(B, n, st); });
+  auto ff = job_queues<RollBatch, 1>(S, T, [&](int, RollBatch& B, int n) { launch_ffill(B, n, st); });
+  auto tile = job_queues<RollBatch, 6>(S, T, [&](int g, RollBatch& B, int n) { launch_tile(g, B, n, st); });
+  auto slide = job_queues<RollBatch, kNSlide>(   // segments set at the launch
+      S, T, [&](int v, RollBatch& B, int n) { launch_slide(v, B, n, st, slide_xc[v]); });
+  auto sten = job_queues<RollBatch, 6>(S, T, [&](int b, RollBatch& B, int n) { launch_stencil(b, B, n, st); });
   for (int i = 0; i < n_jobs; ++i) {
     const bq_roll_job& in = jobs[i];
-    if (in.panel && panel_supported(in.mode, in.window, in.shift)) {   // time-parallel (bq_panel.hip)
-      PanelJob& P = pan.j[npan++];
-      P.x = in.x;
-      P.out = in.out;
-      P.ld_in = in.ld_in;
-      P.ld_out = in.ld_out;
-      P.rows = in.rows > 0 ? in.rows : S;
-      P.win = in.window;
-      P.minp = in.min_periods;
-      P.shift = in.shift;
-      P.mode = in.mode;
-      P.alpha = in.alpha;
-      P.hi = P.lo = nullptr;
-      if (npan == PN_MAXJOBS) flush_pan();
+    const Routed r = route_job(in, S, T);
+    if (r.to == Route::Panel) {
+      pan.push(0, panel_job(in, S));
       continue;
     }
-    RollJob J;
-    memset(&J, 0, sizeof(J));
+    RollJob J = roll_job(in, S, r.mode);
     const bool want_x = cross && cross[i];
-    J.x = in.x;
-    J.out = in.out;
-    J.ld_in = in.ld_in;
-    J.ld_out = in.ld_out;
-    J.win = in.window;
-    J.minp = in.min_periods;
-    J.shift = in.shift;
-    J.mode = in.mode;
-    J.q = in.q;
-    J.alpha = in.alpha;
-    J.rows = in.rows > 0 ? in.rows : S;
-    if (J.mode == BQ_ROLL_QLOWER) {   // an order statistic like the quantile, no interpolation
-      J.mode = BQ_ROLL_QUANTILE;
-      J.lower = 1;
-    }
-    if (J.mode == BQ_ROLL_FFILL) {   // a scan, not a replay (ffill_kernel)
-      ff.j[nff++] = J;
-      if (nff == RW_MAXJOBS) flush_ff();
-      continue;
-    }
-    if (in.mode == BQ_ROLL_ISUM && (in.window > 32 || S * ((T + SR_NT - 1) / SR_NT) > 0x7fffffff))
-      J.mode = BQ_ROLL_SUM;   // long window: the replay (identical values for integer series)
-    if (J.mode == BQ_ROLL_ISUM) {   // integer-valued sum: a direct window sum, stencil launch
-      const int b = stencil_bucket(in.window);
-      sten[b].j[nsten[b]++] = J;
-      if (nsten[b] == RW_MAXJOBS) flush_sten(b);
-    } else if (J.mode >= BQ_ROLL_MEAN) {   // moments / ewm: exact replay
-      const int back = (J.mode == BQ_ROLL_EWM || J.mode == BQ_ROLL_FFILL) ? 0 : in.window + in.shift;
-      max_back = back > max_back ? back : max_back;
-      rep.j[nrep++] = J;
-      if (nrep == RW_MAXJOBS) flush_rep();
-    } else if (const int sv = slide_variant(in.window, J.mode, J.q);
-               rank_impl(in.window, S, T, sv >= 0) == 3) {
-      if (want_x) {
-        J.cross = cross[i];
-        J.ld_cross = ld_cross[i];
-      }
-      slide[sv].j[nslide[sv]++] = J;
-      if (nslide[sv] == RW_MAXJOBS) flush_slide(sv);
-    } else if (rank_impl(in.window, S, T, false) == 2 && S * ((T + SR_NT - 1) / SR_NT) <= 0x7fffffff) {
-      const int b = stencil_bucket(in.window);
-      sten[b].j[nsten[b]++] = J;
-      if (nsten[b] == RW_MAXJOBS) flush_sten(b);
-    } else if (rank_impl(in.window, S, T, false) >= 1) {
-      const int g = tile_group(in.window, in.mode, in.q) + (in.panel && rank_pack() ? 3 : 0);
-      tile[g].j[ntile[g]++] = J;
-      if (ntile[g] == RW_MAXJOBS) flush_tile(g);
-    } else {
-      // segments: lanes = (symbol, segment). Enough lanes to fill the SIMDs to
-      // the kernel's occupancy (waves per SIMD set by the window's register
-      // footprint), but no more than ~80k-130k: every lane streams its own
-      // row lines through L2, and beyond that the lines are evicted before
-      // their 16 values are used (measured: tools/segx.py sweep). Each
-      // segment re-reads one window of warm-up values.
-      static const int occ[6] = {8, 6, 3, 2, 2, 1};   // rank_kernel<8,24,48,64,80,96>
-      static const int64_t cap[6] = {80000, 80000, 100000, 131072, 131072, 65536};
-      const int b0 = rank_bucket(in.window);
-      int64_t lanes = (int64_t)1024 * occ[b0] * WAVE;
-      lanes = lanes < cap[b0] ? lanes : cap[b0];
-      const int64_t nseg_t = lanes / S > 1 ? lanes / S : 1;
-      int seg = (int)((T + nseg_t - 1) / nseg_t);
-      seg = seg < in.window ? in.window : seg;
-      J.seg = seg;
-      J.nseg = (int)((T + seg - 1) / seg);
-      const int b = rank_bucket(in.window);
-      rank[b].j[nrank[b]++] = J;
-      const int64_t items = S * (int64_t)J.nseg;
-      rank_items[b] = items > rank_items[b] ? items : rank_items[b];
-      if (nrank[b] == RW_MAXJOBS) flush_rank(b);
+    switch (r.to) {
+      case Route::Ffill: ff.push(0, J); break;
+      case Route::Replay: rep.push(0, J); break;
+      case Route::Stencil: sten.push(r.bucket, J); break;
+      case Route::Slide:
+        if (want_x) {
+          J.cross = cross[i];
+          J.ld_cross = ld_cross[i];
+        }
+        slide.push(r.bucket, J);
+        break;
+      default: tile.push(r.bucket, J);
     }
     if (want_x && !J.cross) xpass[nxp++] = i;   // not on the slide kernel: a flag pass after
   }
-  flush_pan();
-  flush_rep();
-  flush_ff();
-  for (int b = 0; b < 6; ++b) flush_rank(b);
-  for (int g = 0; g < 6; ++g) flush_tile(g);
-  for (int v = 0; v < kNSlide; ++v) flush_slide(v);
-  for (int b = 0; b < 6; ++b) flush_sten(b);
+  pan.flush();
+  rep.flush();
+  ff.flush();
+  tile.flush();
+  slide.flush();
+  sten.flush();
   for (int u = 0; u < nxp; ++u) {
     const bq_roll_job& in = jobs[xpass[u]];
     const int64_t n = S * T;

@@ -55,7 +55,7 @@ def main(out):
         res[f"mixed_{i}"] = r
     for i, sp in enumerate(mixed):   # one class per call
         res[f"single_{i}"] = engine.rolling_many(sp)[0]
-    big = panel(5000, 64)            # > 4096 symbols: the per-class path for a mixed batch
+    big = panel(5000, 64)            # a mixed batch wider than one grid row of waves (79 per series)
     for i, r in enumerate(engine.rolling_many(*[Roll(big, 3, "sum"), Roll(big, 10, "std"), Ewm(big, span=9)])):
         res[f"big_{i}"] = r
     np.savez(out, **{k: v.cpu().numpy() for k, v in res.items()})

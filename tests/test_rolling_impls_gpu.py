@@ -1,12 +1,12 @@
-"""Both kernel families behind each rolling statistic give the same bits:
-the per-lane sorted window (a run-time and a register-resident compile-time
-window, the latter on one lane or split over a lane pair) vs the per-wave
-sorted union vs the per-output sorting network (order statistics),
-the LDS-ring replay vs the class-specialised re-staging replay (moments, ewm,
-ffill). Each implementation is forced in its own child process
-(BQ_RANK_IMPL / BQ_REPLAY_IMPL) over the same battery — NaN gaps, constant
-runs, signed zeros, shifts, min_periods, windows on both sides of every
-dispatch boundary — and the order statistics are also checked against pandas."""
+"""Every kernel behind each rolling statistic gives the same bits: the
+register-resident sorted window (on one lane, or split over a lane pair or
+quad) vs the per-wave sorted union vs the per-output sorting network (order
+statistics), the class-specialised re-staging replay vs the all-classes one
+(moments, ewm). Each implementation is forced in its own child process
+(BQ_RANK_IMPL / BQ_REPLAY_IMPL / BQ_SLIDE_*) over the same battery — NaN gaps,
+constant runs, signed zeros, shifts, min_periods, windows on both sides of
+every dispatch boundary — and the order statistics, the moments, the ewm
+series and the fill are also checked against pandas, bit for bit."""
 
 import os
 import subprocess
@@ -33,7 +33,6 @@ def test_rolling_implementations_agree_bitwise(cuda, tmp_path):
     from rolling_impl_run import RANK_JOBS, panel
 
     runs = {
-        "lane_ring": _run(tmp_path, "lane_ring", {"BQ_RANK_IMPL": "lane", "BQ_REPLAY_IMPL": "ring"}),
         "tile_restage": _run(tmp_path, "tile_restage", {"BQ_RANK_IMPL": "tile", "BQ_REPLAY_IMPL": "restage"}),
         "stencil_mixed": _run(tmp_path, "stencil_mixed", {"BQ_RANK_IMPL": "stencil", "BQ_REPLAY_IMPL": "mixed"}),
         "slide": _run(tmp_path, "slide", {"BQ_RANK_IMPL": "slide", "BQ_SLIDE_PAIR_MIN": "0"}),
@@ -41,8 +40,7 @@ def test_rolling_implementations_agree_bitwise(cuda, tmp_path):
                                                     "BQ_SLIDE_GROUP": "2"}),
         "slide_quad": _run(tmp_path, "slide_quad", {"BQ_RANK_IMPL": "slide", "BQ_SLIDE_PAIR_MIN": "48",
                                                     "BQ_SLIDE_GROUP": "4"}),
-        "restage64": _run(tmp_path, "restage64", {"BQ_REPLAY_IMPL": "restage", "BQ_REPLAY_SPW": "64"}),
-        "mixed32": _run(tmp_path, "mixed32", {"BQ_REPLAY_IMPL": "mixed", "BQ_REPLAY_SPW": "32"}),
+        "restage": _run(tmp_path, "restage", {"BQ_REPLAY_IMPL": "restage"}),
         "auto": _run(tmp_path, "auto", {}),
     }
     ref = runs["auto"]
@@ -74,3 +72,23 @@ def test_rolling_implementations_agree_bitwise(cuda, tmp_path):
                 else roll.quantile(q, interpolation="lower") if st == "qlower" else roll.quantile(q)).to_numpy().T
         got = ref[f"rank_{w}_{st}_{q}_{mp}_{sh}"]
         np.testing.assert_array_equal(got, want, err_msg=f"w={w} {st} q={q}")
+    # moments, ewm and the fill vs pandas on the same battery (the batch's order
+    # in rolling_impl_run.main): in one mixed call and one series per call
+    wants = [
+        df.rolling(2, min_periods=2).sum(),
+        df.shift(1).rolling(12, min_periods=12).mean(),
+        df.rolling(20, min_periods=20).std(),
+        df.rolling(80, min_periods=5).var(ddof=0),
+        df.shift(3).rolling(96, min_periods=1).std(ddof=0),
+        df.ewm(alpha=1 / 14, adjust=False, min_periods=14).mean(),
+        df.ewm(span=50, adjust=False, min_periods=0).mean(),
+        df.ffill(),
+    ]
+    for i, want in enumerate(wants):
+        for kind in ("mixed", "single"):
+            np.testing.assert_array_equal(ref[f"{kind}_{i}"], want.to_numpy().T, err_msg=f"{kind}_{i}")
+    # the mixed batch wider than one grid row of waves
+    bdf = pd.DataFrame(panel(5000, 64).cpu().numpy().T)
+    for i, want in enumerate([bdf.rolling(3, min_periods=3).sum(), bdf.rolling(10, min_periods=10).std(),
+                              bdf.ewm(span=9, adjust=False, min_periods=0).mean()]):
+        np.testing.assert_array_equal(ref[f"big_{i}"], want.to_numpy().T, err_msg=f"big_{i}")

@@ -6,7 +6,7 @@ stretch, pct changes after a zero close) and do reach +-inf, so every rolling
 kernel family reads its inputs through that rule (bq_device.h win_val):
 the exact replays (mean / sum / var / std / ewm: bit for bit with pandas),
 panel mode (sums / means / ewm within rounding), the order-statistic kernels
-(lane, stencil, tile, sorted-register slide), while ffill keeps infinities
+(stencil, tile, sorted-register slide), while ffill keeps infinities
 as pandas does."""
 
 import numpy as np
