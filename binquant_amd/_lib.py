@@ -53,6 +53,7 @@ PARTIAL_COLUMNS = (
     "sum_atr_pct",
     "sum_bb_width",
     "tracked",   # 0 from the kernel; market_regime.batch.reduce_partials folds the shard's symbol count in
+                 # (bq_breadth_partial_fresh writes the shard's per-timestamp tracked count itself)
 )
 MAX_WINDOW = 126
 MAX_RESAMPLE_FIELDS = 12
@@ -204,6 +205,8 @@ SIGNATURES: dict[str, tuple] = {
     "bq_breadth_partial": (ctypes.c_int, [_P, _PP, _I64, _I64, _I64, _I64, _P, _P]),
     "bq_context_workspace_bytes": (ctypes.c_size_t, [_I64, _I64]),
     "bq_context_partials": (ctypes.c_int, [_PP, _I64, _I64, _I64, _I32, _P, ctypes.c_size_t, _P, _PP, _P]),
+    "bq_panel_compact": (ctypes.c_int, [_PP, _I64, _I64, _I64, _PP, _I64, _P, _I64, _P, _P, _P, _P]),
+    "bq_breadth_partial_fresh": (ctypes.c_int, [_P, _PP, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "bq_pump_ewm": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P]),
     "bq_leadership_workspace_bytes": (ctypes.c_size_t, [_I64, _I64]),
     "bq_leadership": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, ctypes.c_double, _I32, _I32, _I32,

@@ -656,6 +656,106 @@ def breadth_partial(
     return out
 
 
+@dataclass
+class CompactPanel:
+    """compact_panel's result: each symbol's present candles packed to the
+    front of its row (what MarketStateStore would hold), and where they went."""
+
+    high: torch.Tensor        # [S, T] packed; the tail repeats the last present candle
+    low: torch.Tensor
+    close: torch.Tensor
+    rank: torch.Tensor        # [S, T] int32: position of candle t in the packed row, -1 where absent
+    n_present: torch.Tensor   # [S] int32
+    first_t: torch.Tensor     # [S] int32: first present t (T if never present)
+    n_invalid: torch.Tensor   # [S] int32: candles outside the domain (non-zero only with validate=False)
+
+
+@device_entry
+def compact_panel(
+    high: torch.Tensor,
+    low: torch.Tensor,
+    close: torch.Tensor,
+    validate: bool = True,
+    stream: torch.cuda.Stream | None = None,
+) -> CompactPanel:
+    """Per-symbol compaction of a [S, T] panel whose absent candles (late
+    listings, halts, delistings, gaps) are NaN closes: the history
+    MarketStateStore keeps (it drops a candle without a close,
+    market_regime/market_state_store.py:84). A present candle has a finite
+    close, high and low. validate=True reads the kernel's count of candles
+    outside that domain (one sync) and raises ValueError if there are any."""
+    close = _check_panel(close, "close")
+    S, T = close.shape
+    hlc = [_check_panel(t, n, (S, T)) for t, n in zip((high, low, close), ("high", "low", "close"))]
+    ld_in = _row_stride(hlc[0])
+    if any(_row_stride(t) != ld_in for t in hlc):
+        hlc = [t.contiguous() for t in hlc]
+        ld_in = T
+    dev = close.device
+    out = [torch.empty((S, T), dtype=torch.float64, device=dev) for _ in range(3)]
+    ld_r = (T + 3) // 4 * 4   # 16-byte aligned rank rows
+    rank = torch.empty((S, ld_r), dtype=torch.int32, device=dev)[:, :T]
+    n_present, first_t, n_invalid = (torch.empty(S, dtype=torch.int32, device=dev) for _ in range(3))
+    st = _lib.load().bq_panel_compact(
+        _lib.ptr_array([t.data_ptr() for t in hlc]), S, T, ld_in,
+        _lib.ptr_array([t.data_ptr() for t in out]), T,
+        ctypes.c_void_p(rank.data_ptr()), ld_r,
+        ctypes.c_void_p(n_present.data_ptr()), ctypes.c_void_p(first_t.data_ptr()),
+        ctypes.c_void_p(n_invalid.data_ptr()), _stream_handle(stream))
+    _lib.check(st, "bq_panel_compact")
+    if validate and S and int(n_invalid.sum().item()):
+        row = int(torch.nonzero(n_invalid)[0, 0].item())
+        raise ValueError(
+            f"compact_panel: row {row} holds {int(n_invalid[row].item())} candle(s) outside the panel domain "
+            "(a +-inf close, or a present candle without a finite high / low); histories with candles "
+            "without high or low go through DeviceMarketStateStore")
+    return CompactPanel(high=out[0], low=out[1], close=out[2], rank=rank, n_present=n_present, first_t=first_t,
+                        n_invalid=n_invalid)
+
+
+@device_entry
+def breadth_partial_fresh(
+    compact: CompactPanel,
+    feats: dict[str, torch.Tensor],
+    out: torch.Tensor | None = None,
+    stream: torch.cuda.Stream | None = None,
+) -> torch.Tensor:
+    """[T, 10] partials over the symbols fresh at each timestamp
+    (get_fresh_symbols, market_regime/market_state_store.py:49-54, into the
+    reductions of _build_context, live_market_context_accumulator.py:135-163).
+    feats = market_features on the compacted panel. Column 9 is the shard's
+    tracked count at t (symbols listed at or before t)."""
+    close = _check_panel(compact.close, "compact.close")
+    S, T = close.shape
+    fs = [_check_panel(feats[n], n, (S, T)) for n in FEATURE_COLUMNS]
+    ld_f = _row_stride(fs[0])
+    if any(_row_stride(t) != ld_f for t in fs):
+        raise ValueError("feature columns must share one row stride")
+    rank, first_t = compact.rank, compact.first_t
+    if not (rank.is_cuda and rank.dtype == torch.int32 and tuple(rank.shape) == (S, T)
+            and (T <= 1 or rank.stride(1) == 1)):
+        raise ValueError(f"compact.rank: expected an int32 CUDA [{S}, {T}] tensor with unit stride along T")
+    if not (first_t.is_cuda and first_t.dtype == torch.int32 and tuple(first_t.shape) == (S,)
+            and first_t.is_contiguous()):
+        raise ValueError(f"compact.first_t: expected a contiguous int32 CUDA [{S}] tensor")
+    if out is None:
+        out = torch.empty((T, len(PARTIAL_COLUMNS)), dtype=torch.float64, device=close.device)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.device == close.device
+              and tuple(out.shape) == (T, len(PARTIAL_COLUMNS)) and out.is_contiguous()):
+        raise ValueError(f"out: expected a contiguous float64 [{T}, {len(PARTIAL_COLUMNS)}] tensor on {close.device}")
+    st = _lib.load().bq_breadth_partial_fresh(
+        ctypes.c_void_p(close.data_ptr()),
+        _lib.ptr_array([t.data_ptr() for t in fs]),
+        ctypes.c_void_p(rank.data_ptr()),
+        ctypes.c_void_p(first_t.data_ptr()),
+        S, T, _row_stride(close), ld_f, _row_stride(rank),
+        ctypes.c_void_p(out.data_ptr()),
+        _stream_handle(stream),
+    )
+    _lib.check(st, "bq_breadth_partial_fresh")
+    return out
+
+
 @device_entry
 def context_partials(
     high: torch.Tensor,

@@ -34,6 +34,7 @@ class MarketContextBatch:
     contexts: ContextBatch
     features: dict[str, torch.Tensor]   # this rank's [S, T] feature columns
     partial: torch.Tensor               # reduced [T, 10] partials (device)
+    rank: torch.Tensor | None = None    # fresh build: [S, T] int32 column of each candle in `features`
 
     def context_at(self, i: int) -> dict | None:
         return self.contexts.context_at(i)
@@ -42,17 +43,29 @@ class MarketContextBatch:
                            btc_index: int | None = None) -> dict[str, np.ndarray]:
         """Per-symbol feature row at timestamp index i (this rank's symbols),
         with relative strength and the micro-regime annotation. After a fused
-        build (keep_features=False) only the last timestamp is held."""
+        build (keep_features=False) only the last timestamp is held. After a
+        fresh build (``rank`` set) each symbol's row is gathered at
+        rank[:, i]; symbols not fresh at i, or on their first candle, get NaN
+        features."""
         T = close.shape[1]
         j = i % T if i < 0 else i
         fcols = next(iter(self.features.values())).shape[1]
-        if fcols == 1 and T > 1:
-            if j != T - 1:
-                raise ValueError("fused context build: only the last timestamp's features are kept")
-            j_f = 0
+        if self.rank is not None:
+            k = self.rank[:, j].long()
+            have = k >= 1
+            idx = k.clamp(min=0)[:, None]
+            f = {}
+            for name, v in self.features.items():
+                row = v.gather(1, idx)[:, 0].double()
+                f[name] = torch.where(have, row, torch.full_like(row, float("nan"))).cpu().numpy()
         else:
-            j_f = j
-        f = {k: v[:, j_f].double().cpu().numpy() for k, v in self.features.items()}
+            if fcols == 1 and T > 1:
+                if j != T - 1:
+                    raise ValueError("fused context build: only the last timestamp's features are kept")
+                j_f = 0
+            else:
+                j_f = j
+            f = {k: v[:, j_f].double().cpu().numpy() for k, v in self.features.items()}
         c = close[:, j].cpu().numpy()
         ret = f["return_pct"]
         rs = np.zeros_like(ret) if btc_return_t is None else ret - btc_return_t
@@ -75,7 +88,8 @@ def shard_bounds(n_symbols: int, world: int, rank: int) -> tuple[int, int]:
 TRACKED_COLUMN = 9   # PARTIAL_COLUMNS[9]: symbols tracked by the shard
 
 
-def reduce_partials(part: torch.Tensor, n_local: int, group=None, force: bool = False) -> tuple[torch.Tensor, int]:
+def reduce_partials(part: torch.Tensor, n_local: int, group=None, force: bool = False,
+                    tracked_per_timestamp: bool = False):
     """ONE all_reduce(sum) of the [T, 10] partials over the symbol shards (RCCL
     over xGMI on GPUs, gloo on CPU). The shard's tracked-symbol
     count rides in the spare column 9 of every row, so the admission gate's
@@ -84,7 +98,22 @@ def reduce_partials(part: torch.Tensor, n_local: int, group=None, force: bool = 
     rank the partials are returned with column 9 = n_local.
 
     force=True runs the collective whenever a process group is initialised,
-    even at world size 1 (the one-GPU RCCL check, tests/test_rccl_gpu.py)."""
+    even at world size 1 (the one-GPU RCCL check, tests/test_rccl_gpu.py).
+
+    tracked_per_timestamp=True (the fresh build): column 9 already holds the
+    shard's tracked count at every t (bq_breadth_partial_fresh) and is left as
+    written; n_local is not used and the second result is the reduced
+    per-timestamp tracked count, an int64 array [T]."""
+    if tracked_per_timestamp:
+        if part.shape[0] and dist.is_available() and dist.is_initialized() and (
+                force or dist.get_world_size(group) > 1):
+            if part.is_cuda and dist.get_backend(group) == "gloo":   # CPU rehearsal of the RCCL path
+                host = part.cpu()
+                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+                part.copy_(host)
+            else:   # RCCL over xGMI
+                dist.all_reduce(part, op=dist.ReduceOp.SUM, group=group)
+        return part, part[:, TRACKED_COLUMN].cpu().numpy().astype(np.int64)
     part[:, TRACKED_COLUMN] = float(n_local)
     if dist.is_available() and dist.is_initialized() and (force or dist.get_world_size(group) > 1):
         # no timestamps (T == 0, the same on every rank): the count alone travels,
@@ -102,13 +131,39 @@ def reduce_partials(part: torch.Tensor, n_local: int, group=None, force: bool = 
 
 
 def contexts_from_partials(partial: np.ndarray, btc_return: np.ndarray, btc_trend: np.ndarray,
-                           total_tracked: int, timestamps=None, previous_context: dict | None = None) -> ContextBatch:
+                           total_tracked, timestamps=None, previous_context: dict | None = None) -> ContextBatch:
     """Host scoring of reduced partials; btc_* are the benchmark's feature rows
-    (NaN where it has no features)."""
+    (NaN where it has no features). total_tracked: an int, or a length-T
+    array of per-timestamp tracked counts (score_contexts)."""
     btc_valid = ~np.isnan(btc_return)
     batch = score_contexts(partial, np.nan_to_num(btc_return), np.nan_to_num(btc_trend), btc_valid,
                            total_tracked=total_tracked, timestamps=timestamps)
     return annotate_market(batch, previous_context)
+
+
+def _market_context_batch_fresh(high, low, close, btc_hlc, max_bars, timestamps, total_tracked, group,
+                                previous_context) -> MarketContextBatch:
+    """market_context_batch(fresh=True): compact, features on the compacted
+    panel, gathered partials, one all-reduce (column 9 = tracked at t), scoring."""
+    comp = engine.compact_panel(high, low, close)
+    feats = engine.market_features(comp.high, comp.low, comp.close, max_bars=max_bars)
+    part = engine.breadth_partial_fresh(comp, feats)
+    part, tracked = reduce_partials(part, close.shape[0], group, tracked_per_timestamp=True)
+    # BTC: the features at its last present candle <= t, stale across a gap
+    # (its history as it stands, live_market_context_accumulator.py:105-106)
+    bcomp = engine.compact_panel(*btc_hlc)
+    bf = engine.market_features(bcomp.high, bcomp.low, bcomp.close, max_bars=max_bars)
+    k = np.maximum.accumulate(bcomp.rank[0].cpu().numpy().astype(np.int64)) if close.shape[1] else np.zeros(0, np.int64)
+    have = k >= 1   # fewer than 2 candles so far: no features (:248-249)
+    kk = np.where(have, k, 0)
+    btc_ret = np.where(have, bf["return_pct"][0].cpu().numpy()[kk], np.nan)
+    btc_trend = np.where(have, bf["trend_score"][0].cpu().numpy()[kk], np.nan)
+    batch = contexts_from_partials(
+        part.cpu().numpy(), btc_ret, btc_trend,
+        total_tracked=total_tracked if total_tracked is not None else tracked,
+        timestamps=timestamps, previous_context=previous_context,
+    )
+    return MarketContextBatch(contexts=batch, features=feats, partial=part, rank=comp.rank)
 
 
 def market_context_batch(
@@ -122,6 +177,7 @@ def market_context_batch(
     group=None,
     previous_context: dict | None = None,
     keep_features: bool = True,
+    fresh: bool = False,
 ) -> MarketContextBatch:
     """Contexts at every timestamp of a (possibly sharded) [S, T] panel.
 
@@ -130,7 +186,21 @@ def market_context_batch(
     keep_features=False: the fused build (engine.context_partials) — the
     feature columns are never written; ``features`` then holds the last
     timestamp's row only ([S, 1] each: symbol_features_at(T - 1) works).
+    fresh=True: the panel may hold absent candles (NaN close: late listings,
+    halts, delistings, gaps) and gets the reference's store semantics — each
+    symbol's history is its present candles (market_state_store.py:84, :28),
+    a context sums the symbols present at its timestamp (:49-54), the gate
+    uses the symbols listed so far (live_market_context_accumulator.py
+    :96-102) and BTC's features are those of its last present candle
+    (:105-106). ``features`` are then indexed by ``rank``, not by timestamp
+    (symbol_features_at gathers). The fused build is dense-only:
+    fresh=True needs keep_features=True.
     """
+    if fresh:
+        if not keep_features:
+            raise ValueError("fresh=True needs keep_features=True: the fused context build is dense-only")
+        return _market_context_batch_fresh(high, low, close, btc_hlc, max_bars, timestamps, total_tracked, group,
+                                           previous_context)
     if keep_features:
         feats = engine.market_features(high, low, close, max_bars=max_bars)
         part = engine.breadth_partial(close, feats)

@@ -64,12 +64,15 @@ def score_contexts(
     btc_return: np.ndarray,
     btc_trend: np.ndarray,
     btc_valid: np.ndarray,
-    total_tracked: int,
+    total_tracked,
     fresh_count: np.ndarray | None = None,
     timestamps: np.ndarray | None = None,
 ) -> ContextBatch:
     """_build_context (:95-242) from reduced partials [T, 10].
 
+    total_tracked: the symbols ever seen (:97) — an int for the whole panel,
+    or a length-T array of per-timestamp counts (symbols list over time);
+    the array form gives element-wise required / tracked / coverage_ratio.
     fresh_count[t]: symbols whose last closed candle is t (all of them in a
     [S, T] panel); defaults to total_tracked.
     """
@@ -77,8 +80,16 @@ def score_contexts(
     T = P.shape[0]
     ix = PARTIAL_INDEX
     n = P[:, ix["count"]]
-    fresh = np.full(T, float(total_tracked)) if fresh_count is None else np.asarray(fresh_count, np.float64)
-    required = max(REQUIRED_FRESH_SYMBOLS, ceil(total_tracked * MIN_COVERAGE_RATIO))
+    if np.ndim(total_tracked) == 0:
+        fresh = np.full(T, float(total_tracked)) if fresh_count is None else np.asarray(fresh_count, np.float64)
+        required = max(REQUIRED_FRESH_SYMBOLS, ceil(total_tracked * MIN_COVERAGE_RATIO))
+    else:
+        total_tracked = np.asarray(total_tracked, dtype=np.int64)
+        if total_tracked.shape != (T,):
+            raise ValueError(f"total_tracked: expected an int or a length-{T} array, got shape {total_tracked.shape}")
+        fresh = total_tracked.astype(np.float64) if fresh_count is None else np.asarray(fresh_count, np.float64)
+        # the scalar path's float product and ceil, element-wise
+        required = np.maximum(float(REQUIRED_FRESH_SYMBOLS), np.ceil(total_tracked * MIN_COVERAGE_RATIO))
     with np.errstate(divide="ignore", invalid="ignore"):
         nz = np.where(n > 0, n, np.nan)
         adv, dec = P[:, ix["adv"]], P[:, ix["dec"]]
@@ -113,7 +124,7 @@ def score_contexts(
         -0.35 * breadth_balance - 0.15 * ema_balance - 0.2 * btc_regime_score - 0.15 * average_return_score
         + 0.45 * market_stress_score
     )
-    tracked = np.maximum(float(total_tracked), n)
+    tracked = np.maximum(np.asarray(total_tracked, dtype=np.float64), n)
     coverage_ratio = np.where(tracked > 0, n / np.where(tracked > 0, tracked, 1.0), 0.0)
     valid = (
         (fresh >= required)

@@ -209,6 +209,8 @@ enum bq_partial_col {
  * drops it, market_state_store.py:84); histories holding candles without a
  * high / low (which the store keeps) go through bq_store_features, the
  * store path's pandas replay. bq_context_partials has the same domain.
+ * Panels with absent candles (NaN close) go through bq_panel_compact +
+ * bq_breadth_partial_fresh below.
  */
 #define BQ_MAX_HISTORY 512
 int bq_market_features(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in,
@@ -245,6 +247,49 @@ size_t bq_context_workspace_bytes(int64_t S, int64_t T);
 int bq_context_partials(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in,
                         int32_t max_bars, void* workspace, size_t workspace_bytes,
                         double* partial, double* const* last_feat, void* stream);
+
+/*
+ * Freshness for panels with late listings, halts, delistings and missing
+ * candles. The reference keeps per symbol the candles it received:
+ * MarketStateStore drops a candle without a close
+ * (market_regime/market_state_store.py:84) and caps the history at the last
+ * max_bars of the others (:28); _build_context(ts) admits only the symbols
+ * whose last candle is ts (get_fresh_symbols, :49-54), gates on
+ * max(40, ceil(0.7 * tracked)) with tracked = every symbol ever seen
+ * (live_market_context_accumulator.py:96-102, :196-204), and takes BTC's
+ * features from its history as it stands (:105-106).
+ *
+ * bq_panel_compact: per-row stream compaction. hlc = {high, low, close}
+ * [S][ld_in]; candle (s, t) is present iff close[s][t] is finite. Outputs
+ * (all overwritten, caller-owned): hlc_out = the present candles of each row
+ * packed to the front in order, [S][ld_c], the tail [n_present[s], T) filled
+ * with the row's last present candle (1.0 for a row never present) so that
+ * bq_market_features runs on it over finite data; rank[S][ld_r] = position k
+ * of candle t in the packed row, -1 where absent; n_present[S];
+ * first_t[S] = first present t (T if none); n_invalid[S] = candles outside
+ * the domain: a +-inf close (treated as absent), or a present candle whose
+ * high or low is not finite (packed as it is). Callers reject a panel with
+ * n_invalid != 0: such histories belong to the store path (bq_store_features).
+ * The features of bq_market_features(hlc_out, max_bars) at [s][k] are then
+ * _compute_symbol_features over the store's history of s at the time of its
+ * k-th candle. Deterministic; no atomics. T <= 2^31 - 257.
+ *
+ * bq_breadth_partial_fresh: bq_breadth_partial over the symbols fresh at t.
+ * close_c [S][ld_c] and feat_c[BQ_NUM_FEATURES] [S][ld_f] are the packed
+ * close and the features computed on the packed panel; for every t the row
+ * partial[t] sums, over the symbols with k = rank[s][t] >= 1, the values at
+ * [s][k] (columns 0-8, the order of bq_breadth_partial: bit-equal to it when
+ * every candle is present). Column BQ_P_RESERVED receives the shard's
+ * tracked count at t: the symbols with first_t[s] <= t. rank values must lie
+ * in [-1, T); others are skipped. Deterministic; no atomics.
+ */
+int bq_panel_compact(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in,
+                     double* const* hlc_out, int64_t ld_c, int32_t* rank, int64_t ld_r,
+                     int32_t* n_present, int32_t* first_t, int32_t* n_invalid, void* stream);
+int bq_breadth_partial_fresh(const double* close_c, const double* const* feat_c,
+                             const int32_t* rank, const int32_t* first_t, int64_t S, int64_t T,
+                             int64_t ld_c, int64_t ld_f, int64_t ld_r, double* partial,
+                             void* stream);
 
 /*
  * GradualGainerRetest relative-strength leadership at every prefix t
