@@ -32,19 +32,21 @@
 // pass 3  context_chunk_reduce_kernel: the chunks in order -> [T][10].
 //
 // No atomics: the result is bitwise reproducible run to run.
-#include "bq_device.h"
+//
+// Host side: ctx_args fills what every launch of pass 1 shares (the EMA
+// constants and the row load are bq_context.h's, shared with bq_market.hip),
+// launch_context<FEAT> picks the instantiation; bq_context_partials and
+// context_features (bq_market_features' wave-per-symbol path) call both.
+#include "bq_context.h"
 #include "binquant_amd.h"
 
 #include <string.h>
 
 namespace bq {
 
-#ifndef CX_NR
-#define CX_NR 2   // Newton steps after the hardware reciprocal in cx_div (tools/rcp_probe.hip)
-#endif
 constexpr int CX_NW = 4;                // waves = symbols per workgroup = per group record
 constexpr int CX_NT = CX_NW * WAVE;
-constexpr int CX_K = 4;                 // candles per lane
+constexpr int CX_K = CTX_K;               // candles per lane
 constexpr int CX_TT = WAVE * CX_K;      // 256-candle wave tile
 constexpr int CX_HS = 20;               // short-window halo (BB 20, ATR 14)
 constexpr int CX_RS = CX_HS + CX_TT;    // 276
@@ -66,9 +68,7 @@ struct CtxArgs {
   int64_t S, ld_in;
   int T, M;
   int vin;
-  double alpha[2], om[2], den[2], lin_a[2], lin_b[2];
-  double apow[2][8];   // lin_a^(4 * 2^j)
-  double corr[2];      // lin_a^(M - 1)
+  FeatEma E;           // corr zeroed where the lagged chain is not run
   int lag20, lag50;    // the lagged chain is run where corr >= 1e-15 (below, corr * |Y_s - c_s|
                        // is under 1e-15 of the price move: far inside the 1e-9 bar)
   double* gsum[4];     // group sums [ngrp][ld_g]: return, trend, atr_pct, bb_width
@@ -86,37 +86,13 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ void cx_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[CX_K]) {
-  if (vec && tb + CX_K <= T) {
-    const double2* p = reinterpret_cast<const double2*>(row + tb);
-    const double2 a = p[0], b = p[1];
-    x[0] = a.x;
-    x[1] = a.y;
-    x[2] = b.x;
-    x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < CX_K; ++k) x[k] = (tb + k < T) ? row[tb + k] : 0.0;
-  }
-}
-
-// 1 / |b| with the hardware reciprocal + CX_NR Newton steps. Measured on
+// 1 / |b| with the hardware reciprocal + 2 Newton steps (rcp_nr). Measured on
 // gfx950 over 4M mantissas x 2^[-60,60] (tools/rcp_probe.hip): 0 steps 4.6e-8
 // max relative error (fails the 1e-9 contract), 1 step 2.2e-15, 2 steps the
 // correctly rounded reciprocal on every sample — a ratio a * r is then within
 // about an ulp of numpy's a / b (not bit for bit: a * RN(1/b) rounds twice).
 // One step would be 2.5% faster at the shard (1.70 -> 1.66 ms); kept at two.
-__device__ __forceinline__ double cx_rcp(double b) {
-#if CX_NR == 0
-  return __builtin_amdgcn_rcp(fabs(b));
-#elif CX_NR == 1
-  const double v = fabs(b);
-  const double r = __builtin_amdgcn_rcp(v);
-  return fma(r, fma(-v, r, 1.0), r);
-#else
-  return rcp_nr(fabs(b));
-#endif
-}
+__device__ __forceinline__ double cx_rcp(double b) { return rcp_nr(fabs(b)); }
 // a / b from r = cx_rcp(b): the sign of a / b and a zero numerator exact
 __device__ __forceinline__ double cx_mul_rcp(double a, double b, double r) { return b < 0.0 ? -(a * r) : a * r; }
 __device__ __forceinline__ double cx_div(double a, double b) { return cx_mul_rcp(a, b, cx_rcp(b)); }
@@ -163,17 +139,17 @@ __global__ __launch_bounds__(CX_NT, 3) void context_partials_kernel(const CtxArg
   double lpow[2], rpow[2];
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
-    lpow[e] = pow_bits<6>(A.apow[e], lane);
-    rpow[e] = pow_bits<5>(A.apow[e], (lane & 15) + 1);
+    lpow[e] = pow_bits<6>(A.E.apow[e], lane);
+    rpow[e] = pow_bits<5>(A.E.apow[e], (lane & 15) + 1);
   }
   wave_sync();
 
   for (int t0 = 0; t0 < T; t0 += CX_TT) {
     const int tb = t0 + CX_K * lane, qb = CX_HS + CX_K * lane;
     double h[CX_K], l[CX_K], c[CX_K], xl[CX_K];
-    cx_load(rH, tb, T, vin, h);
-    cx_load(rL, tb, T, vin, l);
-    cx_load(rC, tb, T, vin, c);
+    load4<double2>(rH, tb, T, vin, h);
+    load4<double2>(rL, tb, T, vin, l);
+    load4<double2>(rC, tb, T, vin, c);
     if (!RING && (A.lag20 || A.lag50)) {
 #pragma unroll
       for (int k = 0; k < CX_K; ++k) {   // lagged closes c[t - M + 1] (0 before the row starts)
@@ -234,12 +210,12 @@ __global__ __launch_bounds__(CX_NT, 3) void context_partials_kernel(const CtxArg
     double Y[2][CX_K], D[2][CX_K];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-      const double al = A.alpha[e], om = A.om[e], dn = A.den[e];
+      const double al = A.E.alpha[e], om = A.E.om[e], dn = A.E.den[e];
       {
         double y = 0.0;
 #pragma unroll
-        for (int k = 0; k < CX_K; ++k) y = (tb + k == 0) ? c[k] : fma(A.lin_a[e], y, A.lin_b[e] * c[k]);
-        const double inc = wave_scan_affine_dpp_rp(y, A.apow[e], rpow[e], lane);
+        for (int k = 0; k < CX_K; ++k) y = (tb + k == 0) ? c[k] : fma(A.E.lin_a[e], y, A.E.lin_b[e] * c[k]);
+        const double inc = wave_scan_affine_dpp_rp(y, A.E.apow[e], rpow[e], lane);
         const double ex = dpp_f64<DPP_WAVE_SHR1>(inc);
         double v = lane == 0 ? ecar[e] : fma(lpow[e], ecar[e], ex);
 #pragma unroll
@@ -258,8 +234,8 @@ __global__ __launch_bounds__(CX_NT, 3) void context_partials_kernel(const CtxArg
         const int s0 = tb - (M - 1);
         double y = 0.0;
 #pragma unroll
-        for (int k = 0; k < CX_K; ++k) y = (s0 + k == 0) ? xl[k] : fma(A.lin_a[e], y, A.lin_b[e] * xl[k]);
-        const double inc = wave_scan_affine_dpp_rp(y, A.apow[e], rpow[e], lane);
+        for (int k = 0; k < CX_K; ++k) y = (s0 + k == 0) ? xl[k] : fma(A.E.lin_a[e], y, A.E.lin_b[e] * xl[k]);
+        const double inc = wave_scan_affine_dpp_rp(y, A.E.apow[e], rpow[e], lane);
         const double ex = dpp_f64<DPP_WAVE_SHR1>(inc);
         double v = lane == 0 ? lcar[e] : fma(lpow[e], lcar[e], ex);
 #pragma unroll
@@ -380,8 +356,8 @@ __global__ __launch_bounds__(CX_NT, 3) void context_partials_kernel(const CtxArg
       const double prev = k > 0 ? c[k - 1] : p1;
       double e20 = Y[0][k], e50 = Y[1][k];
       if (t + 1 > M) {   // the history window starts at s = t - M + 1 > 0
-        e20 = e20 - A.corr[0] * D[0][k];
-        e50 = e50 - A.corr[1] * D[1][k];
+        e20 = e20 - A.E.corr[0] * D[0][k];
+        e50 = e50 - A.E.corr[1] * D[1][k];
       }
       const double a = lct[k] <= t - min(CX_ATR, n) + 1 ? tr[k] : atr[k];
       double m = mid[k], s = sd[k];
@@ -633,41 +609,9 @@ static CtxLayout ctx_layout(int64_t S, int64_t T) {
   return L;
 }
 
-static double cx_alpha_from_span(double span) {
-  const double com = (span - 1.0) / 2.0;
-  return 1.0 / (1.0 + com);
-}
-
-// the EMA constants and the history-cap correction factors
-static void ctx_consts(CtxArgs& A, int max_bars) {
-  const double spans[2] = {20.0, 50.0};   // live_market_context_accumulator.py:266-267
-  for (int e = 0; e < 2; ++e) {
-    const double al = cx_alpha_from_span(spans[e]);
-    A.alpha[e] = al;
-    A.om[e] = 1.0 - al;
-    A.den[e] = A.om[e] + al;
-    A.lin_a[e] = A.om[e] / A.den[e];
-    A.lin_b[e] = al / A.den[e];
-    double ak = 1.0;
-    for (int k = 0; k < CX_K; ++k) ak *= A.lin_a[e];
-    for (int j = 0; j < 8; ++j) {
-      A.apow[e][j] = ak;
-      ak *= ak;
-    }
-    double cp = 1.0;
-    for (int k = 0; k < max_bars - 1; ++k) cp *= A.lin_a[e];
-    A.corr[e] = cp;
-  }
-  A.lag20 = A.corr[0] >= 1e-15;
-  A.lag50 = A.corr[1] >= 1e-15;
-  if (!A.lag20) A.corr[0] = 0.0;
-  if (!A.lag50) A.corr[1] = 0.0;
-}
-
-// bq_market_features through context_partials_kernel<..., FEAT> (bq_market.hip
-// calls this): the same per-wave feature computation, the columns written
-int context_features(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in, int32_t max_bars,
-                     double* const* feat, int64_t ld_out, hipStream_t st) {
+// the part of CtxArgs every launch shares: inputs, strides, the vector flag and
+// the EMA constants with the history-cap correction factors
+static CtxArgs ctx_args(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in, int max_bars) {
   CtxArgs A;
   memset(&A, 0, sizeof(A));
   A.h = hlc[0];
@@ -677,25 +621,44 @@ int context_features(const double* const* hlc, int64_t S, int64_t T, int64_t ld_
   A.ld_in = ld_in;
   A.T = (int)T;
   A.M = max_bars;
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  A.vin = (ld_in % 2) == 0 && aligned(A.h) && aligned(A.l) && aligned(A.c);
-  int vout = (ld_out % 2) == 0;
-  for (int f = 0; f < BQ_NUM_FEATURES; ++f) {
-    A.feat[f] = feat[f];
-    if (feat[f]) vout &= aligned(feat[f]);
-  }
+  A.vin = vec_rows(hlc, 3, ld_in);
+  A.E = feat_ema_consts(max_bars);
+  A.lag20 = A.E.corr[0] >= 1e-15;
+  A.lag50 = A.E.corr[1] >= 1e-15;
+  if (!A.lag20) A.E.corr[0] = 0.0;
+  if (!A.lag50) A.E.corr[1] = 0.0;
+  return A;
+}
+
+template <bool FEAT, bool DIV>
+static void launch_context_div(const CtxArgs& A, unsigned ngrp, int max_bars, hipStream_t st) {
+  // the D ring (fp32) where span 50's term is small: a^(M-1) <= 1e-6 (M >= 346 at
+  // span 50), so D's fp32 rounding moves the EMA by <= 6e-14 |D|; span 20's term is
+  // then below 1e-15 and skipped
+  const bool ring = A.E.corr[1] <= 1e-6 && !A.lag20;
+  const dim3 grid(ngrp), block(CX_NT);
+  if (!FEAT && ring && max_bars == 400)   // MarketStateStore's default cap, the partials path only
+    hipLaunchKernelGGL((context_partials_kernel<DIV, true, false, 400>), grid, block, 0, st, A);
+  else if (ring) hipLaunchKernelGGL((context_partials_kernel<DIV, true, FEAT>), grid, block, 0, st, A);
+  else hipLaunchKernelGGL((context_partials_kernel<DIV, false, FEAT>), grid, block, 0, st, A);
+}
+
+// pass 1 for the partials (FEAT = false) or the feature columns (FEAT = true)
+template <bool FEAT>
+static void launch_context(const CtxArgs& A, unsigned ngrp, int max_bars, hipStream_t st) {
+  if (A.E.den[0] != 1.0 || A.E.den[1] != 1.0) launch_context_div<FEAT, true>(A, ngrp, max_bars, st);
+  else launch_context_div<FEAT, false>(A, ngrp, max_bars, st);
+}
+
+// bq_market_features through context_partials_kernel<..., FEAT> (bq_market.hip
+// calls this): the same per-wave feature computation, the columns written
+int context_features(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in, int32_t max_bars,
+                     double* const* feat, int64_t ld_out, hipStream_t st) {
+  CtxArgs A = ctx_args(hlc, S, T, ld_in, max_bars);
+  for (int f = 0; f < BQ_NUM_FEATURES; ++f) A.feat[f] = feat[f];
   A.ld_f = ld_out;
-  A.vout = vout;
-  ctx_consts(A, max_bars);
-  const unsigned ngrp = (unsigned)((S + CX_NW - 1) / CX_NW);
-  const bool ring = A.corr[1] <= 1e-6 && !A.lag20;
-  if (A.den[0] != 1.0 || A.den[1] != 1.0) {
-    if (ring) hipLaunchKernelGGL((context_partials_kernel<true, true, true>), dim3(ngrp), dim3(CX_NT), 0, st, A);
-    else hipLaunchKernelGGL((context_partials_kernel<true, false, true>), dim3(ngrp), dim3(CX_NT), 0, st, A);
-  } else {
-    if (ring) hipLaunchKernelGGL((context_partials_kernel<false, true, true>), dim3(ngrp), dim3(CX_NT), 0, st, A);
-    else hipLaunchKernelGGL((context_partials_kernel<false, false, true>), dim3(ngrp), dim3(CX_NT), 0, st, A);
-  }
+  A.vout = vec_rows(feat, BQ_NUM_FEATURES, ld_out);
+  launch_context<true>(A, (unsigned)((S + CX_NW - 1) / CX_NW), max_bars, st);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
 
@@ -722,39 +685,14 @@ int bq_context_partials(const double* const* hlc, int64_t S, int64_t T, int64_t 
   }
   const CtxLayout L = ctx_layout(S, T);
   if (!workspace || workspace_bytes < L.bytes || (((uintptr_t)workspace) & 255u)) return BQ_EINVAL;
-  CtxArgs A;
-  memset(&A, 0, sizeof(A));
-  A.h = hlc[0];
-  A.l = hlc[1];
-  A.c = hlc[2];
-  A.S = S;
-  A.ld_in = ld_in;
-  A.T = (int)T;
-  A.M = max_bars;
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  A.vin = (ld_in % 2) == 0 && aligned(A.h) && aligned(A.l) && aligned(A.c);
-  ctx_consts(A, max_bars);
+  CtxArgs A = ctx_args(hlc, S, T, ld_in, max_bars);
   char* ws = (char*)workspace;
   for (int f = 0; f < 4; ++f) A.gsum[f] = (double*)(ws + L.off_sum[f]);
   A.gcnt = (uint16_t*)(ws + L.off_cnt);
   A.ld_g = L.ld_g;
   for (int f = 0; f < BQ_NUM_FEATURES; ++f) A.last[f] = last_feat ? last_feat[f] : nullptr;
   hipStream_t st = (hipStream_t)stream;
-  // the D ring (fp32) where span 50's term is small: a^(M-1) <= 1e-6 (M >= 346 at
-  // span 50), so D's fp32 rounding moves the EMA by <= 6e-14 |D|; span 20's term is
-  // then below 1e-15 and skipped
-  const bool ring = A.corr[1] <= 1e-6 && !A.lag20;
-  if (A.den[0] != 1.0 || A.den[1] != 1.0) {
-    if (ring && max_bars == 400)   // MarketStateStore's default cap
-      hipLaunchKernelGGL((context_partials_kernel<true, true, false, 400>), dim3((unsigned)L.ngrp), dim3(CX_NT), 0, st, A);
-    else if (ring) hipLaunchKernelGGL((context_partials_kernel<true, true>), dim3((unsigned)L.ngrp), dim3(CX_NT), 0, st, A);
-    else hipLaunchKernelGGL((context_partials_kernel<true, false>), dim3((unsigned)L.ngrp), dim3(CX_NT), 0, st, A);
-  } else {
-    if (ring && max_bars == 400)
-      hipLaunchKernelGGL((context_partials_kernel<false, true, false, 400>), dim3((unsigned)L.ngrp), dim3(CX_NT), 0, st, A);
-    else if (ring) hipLaunchKernelGGL((context_partials_kernel<false, true>), dim3((unsigned)L.ngrp), dim3(CX_NT), 0, st, A);
-    else hipLaunchKernelGGL((context_partials_kernel<false, false>), dim3((unsigned)L.ngrp), dim3(CX_NT), 0, st, A);
-  }
+  launch_context<false>(A, (unsigned)L.ngrp, max_bars, st);
   GroupReduceArgs G;
   for (int f = 0; f < 4; ++f) G.gsum[f] = A.gsum[f];
   G.gcnt = A.gcnt;

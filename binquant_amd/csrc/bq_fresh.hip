@@ -12,9 +12,10 @@
 // (finite close) packed to the front in order, plus rank[s][t] = position of
 // candle t in the packed row (-1 where absent). The dense feature kernels then
 // run on the packed rows unchanged — a window of max_bars packed candles is
-// the store's history — and bq_breadth_partial_fresh sums, for every
-// timestamp t, the features at [s][rank[s][t]] of the symbols present at t.
-#include "bq_device.h"
+// the store's history — and bq_breadth_partial_fresh (bq_breadth.hip) sums,
+// for every timestamp t, the features at [s][rank[s][t]] of the symbols
+// present at t.
+#include "bq_context.h"
 #include "binquant_amd.h"
 
 #include <string.h>
@@ -32,7 +33,7 @@ namespace bq {
 // the running count is a multiple of 16, one contiguous 512-byte run always)
 // instead of a lane-strided scatter.
 constexpr int FC_NW = 4;
-constexpr int FC_K = 4;
+constexpr int FC_K = CTX_K;
 constexpr int FC_TT = WAVE * FC_K;
 
 struct CompactArgs {
@@ -47,17 +48,6 @@ struct CompactArgs {
 };
 
 typedef int fc_int4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void fc_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[FC_K]) {
-  if (vec && tb + FC_K <= T) {
-    const dbl2* p = reinterpret_cast<const dbl2*>(row + tb);
-    const dbl2 a = p[0], b = p[1];
-    x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < FC_K; ++k) x[k] = (tb + k < T) ? row[tb + k] : qnan();
-  }
-}
 
 __global__ __launch_bounds__(FC_NW* WAVE) void panel_compact_kernel(const CompactArgs A, int vec_in, int vec_rank) {
   __shared__ double sV[FC_NW][3][FC_TT];
@@ -82,9 +72,9 @@ __global__ __launch_bounds__(FC_NW* WAVE) void panel_compact_kernel(const Compac
   for (int t0 = 0; t0 < T; t0 += FC_TT) {
     const int tb = t0 + FC_K * lane;
     double h[FC_K], l[FC_K], c[FC_K];
-    fc_load(rH, tb, T, vec_in != 0, h);
-    fc_load(rL, tb, T, vec_in != 0, l);
-    fc_load(rC, tb, T, vec_in != 0, c);
+    load4<dbl2, true>(rH, tb, T, vec_in != 0, h);
+    load4<dbl2, true>(rL, tb, T, vec_in != 0, l);
+    load4<dbl2, true>(rC, tb, T, vec_in != 0, c);
     bool pres[FC_K];
     int pos = 0, total = 0, nbad = 0;
     uint64_t m[FC_K];
@@ -162,119 +152,6 @@ __global__ __launch_bounds__(FC_NW* WAVE) void panel_compact_kernel(const Compac
   }
 }
 
-// ---- breadth partials over the fresh symbols --------------------------------------
-// breadth_kernel (bq_market.hip) with a gather: the same constants, the same
-// per-wave symbol order and the same combine order, so with every candle
-// present (rank[s][t] = t) columns 0-8 are bit-equal to bq_breadth_partial's.
-// Neighbouring lanes of a symbol read rank k and k +- 1 except across a gap,
-// so the gathers stay near-coalesced. Column BQ_P_RESERVED counts the symbols
-// listed at or before t (an integer-valued sum: exact in any order).
-constexpr int BF_TW = 64;   // = BR_TW
-constexpr int BF_NW = 16;   // = BR_NW
-
-struct FreshArgs {
-  const double* c;
-  const double* f[BQ_NUM_FEATURES];
-  const int32_t* rank;
-  const int32_t* first_t;
-  int64_t S, ld_c, ld_f, ld_r;
-  int T;
-  double* partial;
-};
-
-// k = rank[s][t], listed = first_t[s] <= t: loaded by the caller one symbol
-// ahead, so the gathers of symbol s do not wait behind its own rank load
-__device__ __forceinline__ void fresh_accumulate(const FreshArgs& A, int64_t s, int k, bool listed,
-                                                 double (&acc)[BQ_NUM_PARTIALS]) {
-  acc[BQ_P_RESERVED] += listed ? 1.0 : 0.0;
-  if (k < 1 || k >= A.T) return;   // absent at t, or the symbol's first candle (history < 2 bars)
-  const double r = A.f[BQ_F_RETURN][s * A.ld_f + k];
-  if (r != r) return;
-  const double cl = A.c[s * A.ld_c + k];
-  acc[BQ_P_COUNT] += 1.0;
-  acc[BQ_P_ADV] += r > 0.0 ? 1.0 : 0.0;
-  acc[BQ_P_DEC] += r < 0.0 ? 1.0 : 0.0;
-  acc[BQ_P_ABOVE20] += cl > A.f[BQ_F_EMA20][s * A.ld_f + k] ? 1.0 : 0.0;
-  acc[BQ_P_ABOVE50] += cl > A.f[BQ_F_EMA50][s * A.ld_f + k] ? 1.0 : 0.0;
-  acc[BQ_P_SUM_RET] += r;
-  acc[BQ_P_SUM_TREND] += A.f[BQ_F_TREND][s * A.ld_f + k];
-  acc[BQ_P_SUM_ATR_PCT] += A.f[BQ_F_ATR_PCT][s * A.ld_f + k];
-  acc[BQ_P_SUM_BB_WIDTH] += A.f[BQ_F_BB_WIDTH][s * A.ld_f + k];
-}
-
-// symbols s0, s0 + step, ... < S at timestamp t, in that order
-__device__ __forceinline__ void fresh_walk(const FreshArgs& A, int64_t s0, int step, int t,
-                                           double (&acc)[BQ_NUM_PARTIALS]) {
-  if (s0 >= A.S) return;
-  int k = A.rank[s0 * A.ld_r + t];
-  int ft = A.first_t[s0];
-  for (int64_t s = s0; s < A.S; s += step) {
-    const int64_t sn = s + step < A.S ? s + step : s;   // clamped: the last prefetch re-reads s
-    const int kn = A.rank[sn * A.ld_r + t];
-    const int fn = A.first_t[sn];
-    fresh_accumulate(A, s, k, ft <= t, acc);
-    k = kn;
-    ft = fn;
-  }
-}
-
-__global__ __launch_bounds__(BF_TW* BF_NW) void breadth_fresh_kernel(const FreshArgs A) {
-  __shared__ double sAcc[BF_NW][BQ_NUM_PARTIALS][BF_TW + 1];
-  const int lane = threadIdx.x & (WAVE - 1), u = threadIdx.x / WAVE;
-  const int t = blockIdx.x * BF_TW + lane;
-  double acc[BQ_NUM_PARTIALS];
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) acc[i] = 0.0;
-  if (t < A.T) fresh_walk(A, u, BF_NW, t, acc);
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) sAcc[u][i][lane] = acc[i];
-  __syncthreads();
-  if (u == 0 && t < A.T) {
-    for (int v = 1; v < BF_NW; ++v)
-#pragma unroll
-      for (int i = 0; i < BQ_NUM_PARTIALS; ++i) acc[i] += sAcc[v][i][lane];
-#pragma unroll
-    for (int i = 0; i < BQ_NUM_PARTIALS; ++i) A.partial[(int64_t)t * BQ_NUM_PARTIALS + i] = acc[i];
-  }
-}
-
-// Few timestamps (the live shapes, T <= 256): one workgroup per timestamp,
-// thread k sums symbols k, k + BFS_NT, ... in ascending order, then the
-// xor-butterflies of breadth_small_kernel (bq_market.hip) combine the
-// threads — its order, so the all-present result is bit-equal to it as well.
-constexpr int BFS_NT = 1024;   // = BS_NT
-constexpr int BFS_MAX_T = 256;   // = BS_MAX_T
-
-__device__ __forceinline__ double fresh_wave_sum(double v, int width) {
-#pragma unroll
-  for (int d = WAVE / 2; d >= 1; d >>= 1)
-    if (d < width) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
-__global__ __launch_bounds__(BFS_NT) void breadth_fresh_small_kernel(const FreshArgs A) {
-  __shared__ double sRed[BQ_NUM_PARTIALS][BFS_NT / WAVE];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
-  const int t = blockIdx.x;
-  double acc[BQ_NUM_PARTIALS];
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) acc[i] = 0.0;
-  fresh_walk(A, tid, BFS_NT, t, acc);
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) {
-    const double v = fresh_wave_sum(acc[i], WAVE);
-    if (lane == 0) sRed[i][w] = v;
-  }
-  __syncthreads();
-  if (w == 0) {
-#pragma unroll
-    for (int i = 0; i < BQ_NUM_PARTIALS; ++i) {
-      const double v = fresh_wave_sum(lane < BFS_NT / WAVE ? sRed[i][lane] : 0.0, BFS_NT / WAVE);
-      if (lane == 0) A.partial[(int64_t)t * BQ_NUM_PARTIALS + i] = v;
-    }
-  }
-}
-
 }  // namespace bq
 
 extern "C" {
@@ -304,41 +181,10 @@ int bq_panel_compact(const double* const* hlc, int64_t S, int64_t T, int64_t ld_
   A.ld_c = ld_c;
   A.ld_r = ld_r;
   A.T = (int)T;
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  const int vin = (ld_in % 2) == 0 && aligned(hlc[0]) && aligned(hlc[1]) && aligned(hlc[2]);
-  const int vrank = (ld_r % 4) == 0 && aligned(rank);
+  const int vin = vec_rows(hlc, 3, ld_in);
+  const int vrank = (ld_r % 4) == 0 && aligned16(rank);
   const unsigned blocks = (unsigned)((S + FC_NW - 1) / FC_NW);
   hipLaunchKernelGGL(panel_compact_kernel, dim3(blocks), dim3(FC_NW * WAVE), 0, (hipStream_t)stream, A, vin, vrank);
-  return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
-}
-
-int bq_breadth_partial_fresh(const double* close_c, const double* const* feat_c, const int32_t* rank,
-                             const int32_t* first_t, int64_t S, int64_t T, int64_t ld_c, int64_t ld_f,
-                             int64_t ld_r, double* partial, void* stream) {
-  using namespace bq;
-  if (!close_c || !feat_c || !rank || !first_t || !partial || S < 0 || T < 0 || ld_c < T || ld_f < T ||
-      ld_r < T || T > 0x7fffffff)
-    return BQ_EINVAL;
-  for (int i = 0; i < BQ_NUM_FEATURES; ++i)
-    if (!feat_c[i]) return BQ_EINVAL;
-  if (T == 0) return BQ_OK;
-  FreshArgs A;
-  A.c = close_c;
-  for (int i = 0; i < BQ_NUM_FEATURES; ++i) A.f[i] = feat_c[i];
-  A.rank = rank;
-  A.first_t = first_t;
-  A.S = S;
-  A.ld_c = ld_c;
-  A.ld_f = ld_f;
-  A.ld_r = ld_r;
-  A.T = (int)T;
-  A.partial = partial;
-  if (T <= BFS_MAX_T) {
-    hipLaunchKernelGGL(breadth_fresh_small_kernel, dim3((unsigned)T), dim3(BFS_NT), 0, (hipStream_t)stream, A);
-  } else {
-    const unsigned blocks = (unsigned)((T + BF_TW - 1) / BF_TW);
-    hipLaunchKernelGGL(breadth_fresh_kernel, dim3(blocks), dim3(BF_TW * BF_NW), 0, (hipStream_t)stream, A);
-  }
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
 

@@ -1,5 +1,6 @@
-// Market-context kernels for gfx950: per-symbol features at every timestamp and
-// the deterministic cross-symbol breadth partial sums.
+// Market-context features for gfx950: the per-symbol features at every
+// timestamp (the cross-symbol breadth sums over them are in bq_breadth.hip, the
+// wave-per-symbol feature pass for many rows in bq_context.hip).
 //
 // bq_market_features restates, for every timestamp t of a [S][T] panel,
 //   LiveMarketContextAccumulator._compute_symbol_features
@@ -17,11 +18,7 @@
 //     rolling(20, min_periods=1): compensated prefix-sum differences with the
 //     pandas constant-window rules, two-pass variance.
 // One 256-thread workgroup per symbol, tiles of 1024 candles (4 per lane).
-//
-// bq_breadth_partial sums the per-symbol features over the symbols of the
-// shard for every t (the counts and sums of _build_context,
-// live_market_context_accumulator.py:135-163) in a fixed order.
-#include "bq_device.h"
+#include "bq_context.h"
 #include "binquant_amd.h"
 
 #include <stdlib.h>
@@ -31,28 +28,19 @@ namespace bq {
 
 constexpr int MF_NT = 256;
 constexpr int MF_NW = MF_NT / WAVE;
-constexpr int MF_K = 4;
+constexpr int MF_K = CTX_K;
 constexpr int MF_TT = MF_NT * MF_K;
 constexpr int MF_H = BQ_MAX_HISTORY;   // halo of the window-seeded EMA terms
 constexpr int MF_R = MF_H + MF_TT;
 constexpr int MF_HS = 32;              // halo of the short windows (ATR 14, BB 20)
 constexpr int MF_RS = MF_HS + MF_TT;
-#ifndef BQ_MF_LDSPERM
-#define BQ_MF_LDSPERM 1   // lane-interleaved short-halo arrays (as bq_enrich's LX)
-#endif
-// slot of short-halo ring position i: lanes own 4 consecutive positions, so
+// slot of short-halo ring position i, lane-interleaved (as bq_enrich's LX):
+// lanes own 4 consecutive positions, so
 // in the natural layout the 64 lanes of a wave touch slots 4 doubles apart (a
 // 4-way bank conflict on every access); position i at (i % 4) * (RS / 4) +
 // i / 4 puts the lanes' k-th candles side by side. qb is a multiple of 4, so
 // for a constant offset x the slot of qb + x is (qb / 4) + a constant.
-#if BQ_MF_LDSPERM
 #define FX(i) (((((i) & 3)) * (MF_RS / 4)) + ((i) >> 2))
-#else
-#define FX(i) (i)
-#endif
-#ifndef BQ_MF_PREFETCH
-#define BQ_MF_PREFETCH 0   // register prefetch of the next tile's inputs
-#endif
 constexpr int ATR_W = 14;   // live_market_context_accumulator.py:268
 constexpr int BB_W = 20;    // :269-270
 
@@ -63,24 +51,8 @@ struct FeatArgs {
   double* out[BQ_NUM_FEATURES];
   int64_t ld_in, ld_out;
   int T, M;
-  double alpha[2], om[2], den[2], lin_a[2], lin_b[2];
-  double apow[2][8];
-  double corr[2];   // lin_a^(M-1)
+  FeatEma E;
 };
-
-__device__ __forceinline__ void mf_load(const double* __restrict__ row, int tb, int T, bool vec,
-                                        double (&x)[MF_K]) {
-  if (vec && tb + MF_K <= T) {
-    const double2* p = reinterpret_cast<const double2*>(row + tb);
-    double2 a = p[0], b = p[1];
-    x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < MF_K; ++k) x[k] = (tb + k < T) ? row[tb + k] : 0.0;
-  }
-}
-
-typedef double mdbl2 __attribute__((ext_vector_type(2)));
 
 // whole-line stores (bq_device.h store_lines); called by every thread of the block
 __device__ __forceinline__ void mf_store(double* __restrict__ row, int tb, int T, bool vec,
@@ -88,14 +60,11 @@ __device__ __forceinline__ void mf_store(double* __restrict__ row, int tb, int T
   store_lines<MF_K>(row, tb, T, vec, x);
 }
 
-#ifndef BQ_MF_WPS
-#define BQ_MF_WPS 1   // __launch_bounds__ min waves per SIMD
-#endif
 // DIV: the EMAs need pandas' `/ (old_wt + new_wt)` (a non-unit sum; for the
 // reference's spans 20 / 50 the sum is exactly 1.0 and the divide is the
 // identity — checked on the host with the same IEEE arithmetic)
 template <bool DIV>
-__global__ __launch_bounds__(MF_NT, BQ_MF_WPS) void features_kernel(const FeatArgs A, int vec_in, int vec_out) {
+__global__ __launch_bounds__(MF_NT, 1) void features_kernel(const FeatArgs A, int vec_in, int vec_out) {
   __shared__ double sPc[MF_RS], sPt[MF_RS], sC[MF_RS];
   __shared__ double sD[2][MF_R];   // Y_e - close (EMA window identity)
   __shared__ double sX[4][MF_NW + 1];   // c, c[-2], h, l of each wave's last candle
@@ -128,34 +97,14 @@ __global__ __launch_bounds__(MF_NT, BQ_MF_WPS) void features_kernel(const FeatAr
   }
   __syncthreads();
 
-#if BQ_MF_PREFETCH
-  double nh[MF_K], nl[MF_K], nc[MF_K];   // the next tile's inputs, in flight during this one
-  mf_load(rH, MF_K * tid, T, vin, nh);
-  mf_load(rL, MF_K * tid, T, vin, nl);
-  mf_load(rC, MF_K * tid, T, vin, nc);
-#endif
   for (int t0 = 0; t0 < T; t0 += MF_TT) {
     const int tb = t0 + MF_K * tid;
     const int pb = MF_H + MF_K * tid;     // position in the long-halo arrays
     const int qb = MF_HS + MF_K * tid;    // position in the short-halo arrays
     double h[MF_K], l[MF_K], c[MF_K];
-#if BQ_MF_PREFETCH
-#pragma unroll
-    for (int k = 0; k < MF_K; ++k) {
-      h[k] = nh[k];
-      l[k] = nl[k];
-      c[k] = nc[k];
-    }
-    if (t0 + MF_TT < T) {
-      mf_load(rH, tb + MF_TT, T, vin, nh);
-      mf_load(rL, tb + MF_TT, T, vin, nl);
-      mf_load(rC, tb + MF_TT, T, vin, nc);
-    }
-#else
-    mf_load(rH, tb, T, vin, h);
-    mf_load(rL, tb, T, vin, l);
-    mf_load(rC, tb, T, vin, c);
-#endif
+    load4<double2>(rH, tb, T, vin, h);
+    load4<double2>(rL, tb, T, vin, l);
+    load4<double2>(rC, tb, T, vin, c);
 
     // neighbour values and scans on DPP (VALU) moves; lane 0's are replaced below
     double pc1 = dpp_f64<DPP_WAVE_SHR1>(c[MF_K - 1]);
@@ -221,8 +170,8 @@ __global__ __launch_bounds__(MF_NT, BQ_MF_WPS) void features_kernel(const FeatAr
     for (int e = 0; e < 2; ++e) {
       double y = 0.0;
 #pragma unroll
-      for (int k = 0; k < MF_K; ++k) y = (tb + k == 0) ? c[k] : fma(A.lin_a[e], y, A.lin_b[e] * c[k]);
-      double inc = wave_scan_affine_dpp(y, A.apow[e], lane);
+      for (int k = 0; k < MF_K; ++k) y = (tb + k == 0) ? c[k] : fma(A.E.lin_a[e], y, A.E.lin_b[e] * c[k]);
+      double inc = wave_scan_affine_dpp(y, A.E.apow[e], lane);
       if (lane == WAVE - 1) sWe[e][w] = inc;
       double ex = dpp_f64<DPP_WAVE_SHR1>(inc);
       epre[e] = lane == 0 ? 0.0 : ex;
@@ -273,9 +222,9 @@ __global__ __launch_bounds__(MF_NT, BQ_MF_WPS) void features_kernel(const FeatAr
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       double C = sEcar[e];
-      for (int u = 0; u < w; ++u) C = fma(A.apow[e][6], C, sWe[e][u]);
-      double y = lane == 0 ? C : fma(pow_bits<6>(A.apow[e], lane), C, epre[e]);
-      const double al = A.alpha[e], om = A.om[e], dn = A.den[e];
+      for (int u = 0; u < w; ++u) C = fma(A.E.apow[e][6], C, sWe[e][u]);
+      double y = lane == 0 ? C : fma(pow_bits<6>(A.E.apow[e], lane), C, epre[e]);
+      const double al = A.E.alpha[e], om = A.E.om[e], dn = A.E.den[e];
 #pragma unroll
       for (int k = 0; k < MF_K; ++k) {
         const double x = c[k];
@@ -328,8 +277,8 @@ __global__ __launch_bounds__(MF_NT, BQ_MF_WPS) void features_kernel(const FeatAr
       double e20 = Y[0][k], e50 = Y[1][k];
       if (t + 1 > M) {   // history window starts at s = t - M + 1 > 0
         const int ps = p - M + 1;
-        e20 = e20 - A.corr[0] * sD[0][ps];
-        e50 = e50 - A.corr[1] * sD[1][ps];
+        e20 = e20 - A.E.corr[0] * sD[0][ps];
+        e50 = e50 - A.E.corr[1] * sD[1][ps];
       }
       // ATR: TR.rolling(14, min_periods=1).mean() at the last row (:268)
       const int ma = min(ATR_W, n);
@@ -406,114 +355,6 @@ __global__ __launch_bounds__(MF_NT, BQ_MF_WPS) void features_kernel(const FeatAr
   }
 }
 
-// ---- breadth partials ---------------------------------------------------------
-// One workgroup of BR_NW waves owns BR_TW consecutive timestamps; wave u sums
-// symbols s = u, u + BR_NW, ... in ascending order, lane = timestamp. The wave
-// partials are then combined in wave order: a fixed, placement-independent
-// reduction order (bitwise reproducible run to run).
-constexpr int BR_TW = 64;
-constexpr int BR_NW = 16;
-
-struct BreadthArgs {
-  const double* c;
-  const double* f[BQ_NUM_FEATURES];
-  int64_t S, ld_c, ld_f;
-  int T;
-  double* partial;
-};
-
-__global__ __launch_bounds__(BR_TW * BR_NW) void breadth_kernel(const BreadthArgs A) {
-  __shared__ double sAcc[BR_NW][BQ_NUM_PARTIALS][BR_TW + 1];
-  const int lane = threadIdx.x & (WAVE - 1), u = threadIdx.x / WAVE;
-  const int t = blockIdx.x * BR_TW + lane;
-  double acc[BQ_NUM_PARTIALS];
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) acc[i] = 0.0;
-  if (t < A.T) {
-    for (int64_t s = u; s < A.S; s += BR_NW) {
-      const double r = A.f[BQ_F_RETURN][s * A.ld_f + t];
-      if (r != r) continue;   // no features at this t (history < 2 bars)
-      const double cl = A.c[s * A.ld_c + t];
-      acc[BQ_P_COUNT] += 1.0;
-      acc[BQ_P_ADV] += r > 0.0 ? 1.0 : 0.0;
-      acc[BQ_P_DEC] += r < 0.0 ? 1.0 : 0.0;
-      acc[BQ_P_ABOVE20] += cl > A.f[BQ_F_EMA20][s * A.ld_f + t] ? 1.0 : 0.0;
-      acc[BQ_P_ABOVE50] += cl > A.f[BQ_F_EMA50][s * A.ld_f + t] ? 1.0 : 0.0;
-      acc[BQ_P_SUM_RET] += r;
-      acc[BQ_P_SUM_TREND] += A.f[BQ_F_TREND][s * A.ld_f + t];
-      acc[BQ_P_SUM_ATR_PCT] += A.f[BQ_F_ATR_PCT][s * A.ld_f + t];
-      acc[BQ_P_SUM_BB_WIDTH] += A.f[BQ_F_BB_WIDTH][s * A.ld_f + t];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) sAcc[u][i][lane] = acc[i];
-  __syncthreads();
-  if (u == 0 && t < A.T) {
-    for (int v = 1; v < BR_NW; ++v)
-#pragma unroll
-      for (int i = 0; i < BQ_NUM_PARTIALS; ++i) acc[i] += sAcc[v][i][lane];
-#pragma unroll
-    for (int i = 0; i < BQ_NUM_PARTIALS; ++i) A.partial[(int64_t)t * BQ_NUM_PARTIALS + i] = acc[i];
-  }
-}
-
-// Few timestamps (the live tick: T = 1). The kernel above gives one lane per
-// timestamp, so at T = 1 each of its 16 waves walks S / 16 symbols with one
-// active lane (≈0.5 ms at S = 10k). Here a workgroup of BS_NT threads owns one
-// timestamp: thread k sums symbols k, k + BS_NT, ... in ascending order, then
-// xor-butterflies over the wave and over the waves combine the threads. Again a
-// fixed, placement-independent order: bitwise reproducible run to run.
-constexpr int BS_NT = 1024;
-constexpr int BS_MAX_T = 256;
-
-__device__ __forceinline__ double wave_sum(double v, int width) {
-#pragma unroll
-  for (int d = WAVE / 2; d >= 1; d >>= 1)
-    if (d < width) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
-__global__ __launch_bounds__(BS_NT) void breadth_small_kernel(const BreadthArgs A) {
-  __shared__ double sRed[BQ_NUM_PARTIALS][BS_NT / WAVE];
-  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
-  const int64_t t = blockIdx.x;
-  double acc[BQ_NUM_PARTIALS];
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) acc[i] = 0.0;
-  for (int64_t s = tid; s < A.S; s += BS_NT) {
-    const double r = A.f[BQ_F_RETURN][s * A.ld_f + t];
-    if (r != r) continue;   // no features at this t (history < 2 bars)
-    const double cl = A.c[s * A.ld_c + t];
-    acc[BQ_P_COUNT] += 1.0;
-    acc[BQ_P_ADV] += r > 0.0 ? 1.0 : 0.0;
-    acc[BQ_P_DEC] += r < 0.0 ? 1.0 : 0.0;
-    acc[BQ_P_ABOVE20] += cl > A.f[BQ_F_EMA20][s * A.ld_f + t] ? 1.0 : 0.0;
-    acc[BQ_P_ABOVE50] += cl > A.f[BQ_F_EMA50][s * A.ld_f + t] ? 1.0 : 0.0;
-    acc[BQ_P_SUM_RET] += r;
-    acc[BQ_P_SUM_TREND] += A.f[BQ_F_TREND][s * A.ld_f + t];
-    acc[BQ_P_SUM_ATR_PCT] += A.f[BQ_F_ATR_PCT][s * A.ld_f + t];
-    acc[BQ_P_SUM_BB_WIDTH] += A.f[BQ_F_BB_WIDTH][s * A.ld_f + t];
-  }
-#pragma unroll
-  for (int i = 0; i < BQ_NUM_PARTIALS; ++i) {
-    const double v = wave_sum(acc[i], WAVE);
-    if (lane == 0) sRed[i][w] = v;
-  }
-  __syncthreads();
-  if (w == 0) {
-#pragma unroll
-    for (int i = 0; i < BQ_NUM_PARTIALS; ++i) {
-      const double v = wave_sum(lane < BS_NT / WAVE ? sRed[i][lane] : 0.0, BS_NT / WAVE);
-      if (lane == 0) A.partial[t * BQ_NUM_PARTIALS + i] = v;
-    }
-  }
-}
-
-static double alpha_from_span(double span) {
-  const double com = (span - 1.0) / 2.0;
-  return 1.0 / (1.0 + com);
-}
-
 // bq_context.hip: the features through the one-wave-per-symbol context kernel
 int context_features(const double* const* hlc, int64_t S, int64_t T, int64_t ld_in, int32_t max_bars,
                      double* const* feat, int64_t ld_out, hipStream_t st);
@@ -562,58 +403,12 @@ int bq_market_features(const double* const* hlc, int64_t S, int64_t T, int64_t l
   A.ld_out = ld_out;
   A.T = (int)T;
   A.M = max_bars;
-  const double spans[2] = {20.0, 50.0};   // live_market_context_accumulator.py:266-267
-  for (int e = 0; e < 2; ++e) {
-    const double al = alpha_from_span(spans[e]);
-    A.alpha[e] = al;
-    A.om[e] = 1.0 - al;
-    A.den[e] = A.om[e] + al;
-    A.lin_a[e] = A.om[e] / A.den[e];
-    A.lin_b[e] = al / A.den[e];
-    double ak = 1.0;
-    for (int k = 0; k < MF_K; ++k) ak *= A.lin_a[e];
-    for (int j = 0; j < 8; ++j) {
-      A.apow[e][j] = ak;
-      ak *= ak;
-    }
-    double cp = 1.0;
-    for (int k = 0; k < max_bars - 1; ++k) cp *= A.lin_a[e];
-    A.corr[e] = cp;
-  }
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  int vin = (ld_in % 2) == 0 && aligned(A.h) && aligned(A.l) && aligned(A.c);
-  int vout = (ld_out % 2) == 0;
-  for (int i = 0; i < BQ_NUM_FEATURES; ++i)
-    if (feat[i]) vout &= aligned(feat[i]);
-  if (A.den[0] != 1.0 || A.den[1] != 1.0)
+  A.E = feat_ema_consts(max_bars);
+  const int vin = vec_rows(hlc, 3, ld_in), vout = vec_rows(feat, BQ_NUM_FEATURES, ld_out);
+  if (A.E.den[0] != 1.0 || A.E.den[1] != 1.0)
     hipLaunchKernelGGL(features_kernel<true>, dim3((unsigned)S), dim3(MF_NT), 0, (hipStream_t)stream, A, vin, vout);
   else
     hipLaunchKernelGGL(features_kernel<false>, dim3((unsigned)S), dim3(MF_NT), 0, (hipStream_t)stream, A, vin, vout);
-  return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
-}
-
-int bq_breadth_partial(const double* close, const double* const* feat, int64_t S, int64_t T,
-                       int64_t ld_close, int64_t ld_feat, double* partial, void* stream) {
-  using namespace bq;
-  if (!close || !feat || !partial || S < 0 || T < 0 || ld_close < T || ld_feat < T || T > 0x7fffffff)
-    return BQ_EINVAL;
-  for (int i = 0; i < BQ_NUM_FEATURES; ++i)
-    if (!feat[i]) return BQ_EINVAL;
-  if (T == 0) return BQ_OK;
-  BreadthArgs A;
-  A.c = close;
-  for (int i = 0; i < BQ_NUM_FEATURES; ++i) A.f[i] = feat[i];
-  A.S = S;
-  A.ld_c = ld_close;
-  A.ld_f = ld_feat;
-  A.T = (int)T;
-  A.partial = partial;
-  if (T <= BS_MAX_T) {
-    hipLaunchKernelGGL(breadth_small_kernel, dim3((unsigned)T), dim3(BS_NT), 0, (hipStream_t)stream, A);
-  } else {
-    const unsigned blocks = (unsigned)((T + BR_TW - 1) / BR_TW);
-    hipLaunchKernelGGL(breadth_kernel, dim3(blocks), dim3(BR_TW * BR_NW), 0, (hipStream_t)stream, A);
-  }
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
 

@@ -192,6 +192,39 @@ def _row_stride(x: torch.Tensor) -> int:
     return int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1])
 
 
+def _hlc_panel(high, low, close):
+    """(high, low, close) checked as one [S, T] panel: ([high, low, close], S,
+    T, their common row stride); columns of different strides are made
+    contiguous."""
+    close = _check_panel(close, "close")
+    S, T = close.shape
+    hlc = [_check_panel(t, n, (S, T)) for t, n in zip((high, low, close), ("high", "low", "close"))]
+    ld_in = _row_stride(hlc[0])
+    if any(_row_stride(t) != ld_in for t in hlc):
+        hlc = [t.contiguous() for t in hlc]
+        ld_in = T
+    return hlc, S, T, ld_in
+
+
+def _feature_columns(feats: dict[str, torch.Tensor], S: int, T: int):
+    """The six [S, T] feature columns in FEATURE_COLUMNS order and their common row stride."""
+    fs = [_check_panel(feats[n], n, (S, T)) for n in FEATURE_COLUMNS]
+    ld_f = _row_stride(fs[0])
+    if any(_row_stride(t) != ld_f for t in fs):
+        raise ValueError("feature columns must share one row stride")
+    return fs, ld_f
+
+
+def _partial_out(out: torch.Tensor | None, T: int, device) -> torch.Tensor:
+    """The [T, 10] partials tensor: the caller's, checked, or a new one."""
+    if out is None:
+        return torch.empty((T, len(PARTIAL_COLUMNS)), dtype=torch.float64, device=device)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.device == device
+            and tuple(out.shape) == (T, len(PARTIAL_COLUMNS)) and out.is_contiguous()):
+        raise ValueError(f"out: expected a contiguous float64 [{T}, {len(PARTIAL_COLUMNS)}] tensor on {device}")
+    return out
+
+
 ENRICH_ROW_PAD = 192   # doubles added to each output row's pitch by enrich_outputs (tools/shard_pitch.py)
 
 
@@ -285,17 +318,11 @@ def market_features(
     """_compute_symbol_features at every timestamp of a [S, T] panel
     (market_regime/live_market_context_accumulator.py:244-297) under the
     MarketStateStore history cap ``max_bars`` (klines_provider.py:40,65 uses 400)."""
-    close = _check_panel(close, "close")
-    S, T = close.shape
-    hlc = [_check_panel(t, n, (S, T)) for t, n in zip((high, low, close), ("high", "low", "close"))]
-    ld_in = _row_stride(hlc[0])
-    if any(_row_stride(t) != ld_in for t in hlc):
-        hlc = [t.contiguous() for t in hlc]
-        ld_in = T
+    hlc, S, T, ld_in = _hlc_panel(high, low, close)
     out = dict(out or {})
     for name in FEATURE_COLUMNS:
         if name not in out:
-            out[name] = torch.empty((S, T), dtype=torch.float64, device=close.device)
+            out[name] = torch.empty((S, T), dtype=torch.float64, device=hlc[2].device)
         else:
             _check_panel(out[name], f"out[{name}]", (S, T))
     ld_out = _row_stride(out[FEATURE_COLUMNS[0]])
@@ -633,15 +660,8 @@ def breadth_partial(
     (the reductions of _build_context, live_market_context_accumulator.py:135-163)."""
     close = _check_panel(close, "close")
     S, T = close.shape
-    fs = [_check_panel(feats[n], n, (S, T)) for n in FEATURE_COLUMNS]
-    ld_f = _row_stride(fs[0])
-    if any(_row_stride(t) != ld_f for t in fs):
-        raise ValueError("feature columns must share one row stride")
-    if out is None:
-        out = torch.empty((T, len(PARTIAL_COLUMNS)), dtype=torch.float64, device=close.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.device == close.device
-              and tuple(out.shape) == (T, len(PARTIAL_COLUMNS)) and out.is_contiguous()):
-        raise ValueError(f"out: expected a contiguous float64 [{T}, {len(PARTIAL_COLUMNS)}] tensor on {close.device}")
+    fs, ld_f = _feature_columns(feats, S, T)
+    out = _partial_out(out, T, close.device)
     st = _lib.load().bq_breadth_partial(
         ctypes.c_void_p(close.data_ptr()),
         _lib.ptr_array([t.data_ptr() for t in fs]),
@@ -684,14 +704,8 @@ def compact_panel(
     market_regime/market_state_store.py:84). A present candle has a finite
     close, high and low. validate=True reads the kernel's count of candles
     outside that domain (one sync) and raises ValueError if there are any."""
-    close = _check_panel(close, "close")
-    S, T = close.shape
-    hlc = [_check_panel(t, n, (S, T)) for t, n in zip((high, low, close), ("high", "low", "close"))]
-    ld_in = _row_stride(hlc[0])
-    if any(_row_stride(t) != ld_in for t in hlc):
-        hlc = [t.contiguous() for t in hlc]
-        ld_in = T
-    dev = close.device
+    hlc, S, T, ld_in = _hlc_panel(high, low, close)
+    dev = hlc[2].device
     out = [torch.empty((S, T), dtype=torch.float64, device=dev) for _ in range(3)]
     ld_r = (T + 3) // 4 * 4   # 16-byte aligned rank rows
     rank = torch.empty((S, ld_r), dtype=torch.int32, device=dev)[:, :T]
@@ -727,10 +741,7 @@ def breadth_partial_fresh(
     tracked count at t (symbols listed at or before t)."""
     close = _check_panel(compact.close, "compact.close")
     S, T = close.shape
-    fs = [_check_panel(feats[n], n, (S, T)) for n in FEATURE_COLUMNS]
-    ld_f = _row_stride(fs[0])
-    if any(_row_stride(t) != ld_f for t in fs):
-        raise ValueError("feature columns must share one row stride")
+    fs, ld_f = _feature_columns(feats, S, T)
     rank, first_t = compact.rank, compact.first_t
     if not (rank.is_cuda and rank.dtype == torch.int32 and tuple(rank.shape) == (S, T)
             and (T <= 1 or rank.stride(1) == 1)):
@@ -738,11 +749,7 @@ def breadth_partial_fresh(
     if not (first_t.is_cuda and first_t.dtype == torch.int32 and tuple(first_t.shape) == (S,)
             and first_t.is_contiguous()):
         raise ValueError(f"compact.first_t: expected a contiguous int32 CUDA [{S}] tensor")
-    if out is None:
-        out = torch.empty((T, len(PARTIAL_COLUMNS)), dtype=torch.float64, device=close.device)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.device == close.device
-              and tuple(out.shape) == (T, len(PARTIAL_COLUMNS)) and out.is_contiguous()):
-        raise ValueError(f"out: expected a contiguous float64 [{T}, {len(PARTIAL_COLUMNS)}] tensor on {close.device}")
+    out = _partial_out(out, T, close.device)
     st = _lib.load().bq_breadth_partial_fresh(
         ctypes.c_void_p(close.data_ptr()),
         _lib.ptr_array([t.data_ptr() for t in fs]),
@@ -773,19 +780,9 @@ def context_partials(
     sums agree to rounding. last=True also returns the features at t = T - 1
     ({name: [S]}, what a context's symbol_features reads); returns
     (partial, last_features | None)."""
-    close = _check_panel(close, "close")
-    S, T = close.shape
-    hlc = [_check_panel(t, n, (S, T)) for t, n in zip((high, low, close), ("high", "low", "close"))]
-    ld_in = _row_stride(hlc[0])
-    if any(_row_stride(t) != ld_in for t in hlc):
-        hlc = [t.contiguous() for t in hlc]
-        ld_in = T
-    dev = close.device
-    if out is None:
-        out = torch.empty((T, len(PARTIAL_COLUMNS)), dtype=torch.float64, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.device == dev
-              and tuple(out.shape) == (T, len(PARTIAL_COLUMNS)) and out.is_contiguous()):
-        raise ValueError(f"out: expected a contiguous float64 [{T}, {len(PARTIAL_COLUMNS)}] tensor on {dev}")
+    hlc, S, T, ld_in = _hlc_panel(high, low, close)
+    dev = hlc[2].device
+    out = _partial_out(out, T, dev)
     lib = _lib.load()
     nbytes = int(lib.bq_context_workspace_bytes(S, T))
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)   # caching allocator: 512-B aligned

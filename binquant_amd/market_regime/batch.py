@@ -88,6 +88,17 @@ def shard_bounds(n_symbols: int, world: int, rank: int) -> tuple[int, int]:
 TRACKED_COLUMN = 9   # PARTIAL_COLUMNS[9]: symbols tracked by the shard
 
 
+def _all_reduce_sum(buf: torch.Tensor, group) -> None:
+    """all_reduce(sum) of buf in place: RCCL over xGMI, or through the host
+    when the group is gloo (the CPU rehearsal of the RCCL path)."""
+    if buf.is_cuda and dist.get_backend(group) == "gloo":
+        host = buf.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
+        buf.copy_(host)
+    else:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+
+
 def reduce_partials(part: torch.Tensor, n_local: int, group=None, force: bool = False,
                     tracked_per_timestamp: bool = False):
     """ONE all_reduce(sum) of the [T, 10] partials over the symbol shards (RCCL
@@ -104,28 +115,18 @@ def reduce_partials(part: torch.Tensor, n_local: int, group=None, force: bool = 
     shard's tracked count at every t (bq_breadth_partial_fresh) and is left as
     written; n_local is not used and the second result is the reduced
     per-timestamp tracked count, an int64 array [T]."""
+    collective = dist.is_available() and dist.is_initialized() and (force or dist.get_world_size(group) > 1)
     if tracked_per_timestamp:
-        if part.shape[0] and dist.is_available() and dist.is_initialized() and (
-                force or dist.get_world_size(group) > 1):
-            if part.is_cuda and dist.get_backend(group) == "gloo":   # CPU rehearsal of the RCCL path
-                host = part.cpu()
-                dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
-                part.copy_(host)
-            else:   # RCCL over xGMI
-                dist.all_reduce(part, op=dist.ReduceOp.SUM, group=group)
+        if part.shape[0] and collective:
+            _all_reduce_sum(part, group)
         return part, part[:, TRACKED_COLUMN].cpu().numpy().astype(np.int64)
     part[:, TRACKED_COLUMN] = float(n_local)
-    if dist.is_available() and dist.is_initialized() and (force or dist.get_world_size(group) > 1):
+    if collective:
         # no timestamps (T == 0, the same on every rank): the count alone travels,
         # so every rank still agrees on the admission gate's total
         buf = part if part.shape[0] else torch.full((1, part.shape[1]), float(n_local), dtype=part.dtype,
                                                     device=part.device)
-        if buf.is_cuda and dist.get_backend(group) == "gloo":   # CPU rehearsal of the RCCL path
-            host = buf.cpu()
-            dist.all_reduce(host, op=dist.ReduceOp.SUM, group=group)
-            buf.copy_(host)
-        else:   # RCCL over xGMI
-            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+        _all_reduce_sum(buf, group)
         return part, int(buf[0, TRACKED_COLUMN].item())
     return part, int(n_local)
 
@@ -139,6 +140,14 @@ def contexts_from_partials(partial: np.ndarray, btc_return: np.ndarray, btc_tren
     batch = score_contexts(partial, np.nan_to_num(btc_return), np.nan_to_num(btc_trend), btc_valid,
                            total_tracked=total_tracked, timestamps=timestamps)
     return annotate_market(batch, previous_context)
+
+
+def _scored(part, btc_ret, btc_trend, total_tracked, timestamps, previous_context, feats,
+            rank=None) -> MarketContextBatch:
+    """The tail of both builds: host scoring of the reduced partials."""
+    batch = contexts_from_partials(part.cpu().numpy(), btc_ret, btc_trend, total_tracked=total_tracked,
+                                   timestamps=timestamps, previous_context=previous_context)
+    return MarketContextBatch(contexts=batch, features=feats, partial=part, rank=rank)
 
 
 def _market_context_batch_fresh(high, low, close, btc_hlc, max_bars, timestamps, total_tracked, group,
@@ -158,12 +167,8 @@ def _market_context_batch_fresh(high, low, close, btc_hlc, max_bars, timestamps,
     kk = np.where(have, k, 0)
     btc_ret = np.where(have, bf["return_pct"][0].cpu().numpy()[kk], np.nan)
     btc_trend = np.where(have, bf["trend_score"][0].cpu().numpy()[kk], np.nan)
-    batch = contexts_from_partials(
-        part.cpu().numpy(), btc_ret, btc_trend,
-        total_tracked=total_tracked if total_tracked is not None else tracked,
-        timestamps=timestamps, previous_context=previous_context,
-    )
-    return MarketContextBatch(contexts=batch, features=feats, partial=part, rank=comp.rank)
+    return _scored(part, btc_ret, btc_trend, total_tracked if total_tracked is not None else tracked, timestamps,
+                   previous_context, feats, comp.rank)
 
 
 def market_context_batch(
@@ -210,12 +215,5 @@ def market_context_batch(
     part, n_total = reduce_partials(part, close.shape[0], group)
     bh, bl, bc = btc_hlc
     bf = engine.market_features(bh, bl, bc, max_bars=max_bars)
-    batch = contexts_from_partials(
-        part.cpu().numpy(),
-        bf["return_pct"][0].cpu().numpy(),
-        bf["trend_score"][0].cpu().numpy(),
-        total_tracked=total_tracked if total_tracked is not None else n_total,
-        timestamps=timestamps,
-        previous_context=previous_context,
-    )
-    return MarketContextBatch(contexts=batch, features=feats, partial=part)
+    return _scored(part, bf["return_pct"][0].cpu().numpy(), bf["trend_score"][0].cpu().numpy(),
+                   total_tracked if total_tracked is not None else n_total, timestamps, previous_context, feats)

@@ -5,7 +5,7 @@ variants interleaved inside every repeat:
 
   compact        bq_panel_compact        (panel_compact_kernel)
   features       bq_market_features on the compacted panel
-  breadth_fresh  bq_breadth_partial_fresh (breadth_fresh_kernel)
+  breadth_fresh  bq_breadth_partial_fresh (breadth_kernel<FRESH>, bq_breadth.hip)
   breadth_dense  bq_breadth_partial on the same all-present features — the
                  kernel the fresh one is measured against
 
