@@ -173,6 +173,27 @@ class BqScorerWeights(ctypes.Structure):
                 ("support_weight", ctypes.c_double)]
 
 
+class BqImpulseParams(ctypes.Structure):
+    """Mirror of ``bq_impulse_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("min_impulse", ctypes.c_double), ("max_impulse", ctypes.c_double), ("min_rs", ctypes.c_double),
+                ("max_btc_return", ctypes.c_double), ("min_conf_return", ctypes.c_double),
+                ("min_close_location", ctypes.c_double), ("max_atr_pct", ctypes.c_double),
+                ("entry_factor", ctypes.c_double), ("min_history", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# bq_impulse_rider: status codes (BQ_IR_*), value-column order, tile size
+IMPULSE_TILE = 1024
+BB_STABLE_MAX_N = 64
+(BQ_IR_CONFIRMED, BQ_IR_SHORT_HISTORY, BQ_IR_INVALID_VALUES, BQ_IR_INVALID_ANCHORS, BQ_IR_BTC_UNAVAILABLE,
+ BQ_IR_RANGE_INVALID, BQ_IR_NOT_READY, BQ_IR_IMPULSE_RANGE, BQ_IR_DID_NOT_CROSS, BQ_IR_BTC_TOO_HIGH,
+ BQ_IR_RS_TOO_LOW, BQ_IR_ATR_TOO_HIGH, BQ_IR_DID_NOT_HOLD, BQ_IR_CONFIRMATION_NEGATIVE,
+ BQ_IR_CLOSE_NOT_NEAR_HIGH) = range(15)
+BQ_IR_NO_FRAME = 255
+IMPULSE_VALUES = ("impulse_return_1h", "previous_impulse_return_1h", "btc_return_1h", "relative_strength_1h",
+                  "trigger_return_15m", "confirmation_return_15m", "confirmation_close_location", "atr_pct",
+                  "entry_limit_price")
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
@@ -211,6 +232,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_leadership_workspace_bytes": (ctypes.c_size_t, [_I64, _I64]),
     "bq_leadership": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, ctypes.c_double, _I32, _I32, _I32,
                                      _I32, _I32, _P, ctypes.c_size_t, _P, _P, _P, _I64, _P]),
+    "bq_impulse_default_params": (None, [ctypes.POINTER(BqImpulseParams)]),
+    "bq_impulse_rider": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _P, _P, _I64,
+                                        ctypes.POINTER(BqImpulseParams), _P, _PP, _I64, _P]),
+    "bq_bb_stable": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, ctypes.c_double, _P, _P, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

@@ -64,7 +64,8 @@ def _side_streams(device: torch.device, n: int) -> list[torch.cuda.Stream]:
 
 
 def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, btc_c15,
-                   max_bars: int = 400, exact: bool = True, h1_max_bins: int | None = None) -> dict[str, torch.Tensor]:
+                   max_bars: int = 400, exact: bool = True, h1_max_bins: int | None = None,
+                   gates: bool = False) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -74,8 +75,13 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     spanning more hours keeps its NEWEST h1_max_bins bins (bq_resample_tail):
     h1.bins is the count written (<= h1_max_bins, bin h1.bins - 1 is the
     row's latest hour) and h1.dropped the oldest bins left out (0 on a
-    gap-free grid). Returns a flat dict of tensors (names prefixed by the
-    stage)."""
+    gap-free grid). gates=True adds, after the 15m frame and on its stream,
+    the entry gates of RelativeStrengthImpulseRider (impulse.<key> for
+    signals.IR_KEYS and impulse.status, from the 15m panel, e15.ATR and
+    ts15 / btc_ts15 / btc_c15; context_evaluator.py:446-454) and of the grid
+    ladder (ladder.stable / ladder.change_pct from e15.bb_*); the default
+    leaves the returned dict and the launch sequence as they were. Returns a
+    flat dict of tensors (names prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -100,6 +106,14 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
         out["btc.beta"], out["btc.corr"] = bc["beta"][:, -1], bc["corr"][:, -1]
         # pct_change(96) with pandas' default pad fill (context_evaluator.py:427-430)
         out["btc.change_24h"] = engine.pct_change(btc_c15.reshape(1, -1), 96)[0, -1:] * 100.0
+        if gates:   # :446-454 and the grid ladder's frame scan; no host sync (btc_ts15 is the cohort's own grid)
+            feats, status = signals.impulse_rider_features(o15, h15, l15, c15, out["e15.ATR"], ts15,
+                                                           btc_ts15.reshape(-1), btc_c, check_bench=False)
+            for k, v in feats.items():
+                out[f"impulse.{k}"] = v
+            out["impulse.status"] = status
+            for k, v in signals.bb_width_stable(out["e15.bb_upper"], out["e15.bb_mid"], out["e15.bb_lower"]).items():
+                out[f"ladder.{k}"] = v
 
     def context(out):   # klines_provider.py:181-199
         part, last = engine.context_partials(h15, l15, c15, max_bars=max_bars, last=True)

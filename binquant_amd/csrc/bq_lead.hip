@@ -31,6 +31,7 @@
 //      ballot scan through LDS).
 // Inputs cross HBM once (the halo re-reads hit L2); nothing but the outputs
 // is written.
+#include "bq_bench_lookup.h"
 #include "bq_device.h"
 #include "binquant_amd.h"
 
@@ -75,33 +76,15 @@ __global__ __launch_bounds__(LD_NT) void lead_kernel(const LeadArgs A) {
   const double* __restrict__ cl = A.close + s * A.ld_c;
   // 1. closes and benchmark closes of candles t0 - LD_CH .. t0 + LD_TT - 1
   const int64_t bt0 = A.bts[0];
-  const int64_t bstep = nb > 1 ? (A.bts[nb - 1] - bt0) / (nb - 1) : 0;
+  const int64_t bstep = bench_step(A.bts, nb, bt0);
   for (int i = tid; i < LD_CH + LD_TT; i += LD_NT) {
     const int t = t0 - LD_CH + i;
     double c = qnan(), b = qnan();
     if (t >= 0 && t < T) {
       c = cl[t];
-      const int64_t key = ts[t];
-      // the last benchmark row with this time: on a regular grid the guessed
-      // row's time, its successor's and its close are loaded together (one
-      // dependent round trip after the candle's time); the search otherwise
-      int jg = -1;
-      if (bstep > 0 && key >= bt0) {
-        const int64_t q = (key - bt0) / bstep;
-        jg = q < nb ? (int)q : -1;
-      }
-      bool hit = false;
-      if (jg >= 0) {
-        const int64_t tg = A.bts[jg];
-        const int64_t tn = jg + 1 < nb ? A.bts[jg + 1] : INT64_MAX;
-        const double bg = A.bclose[jg];
-        hit = tg == key && tn != key;
-        if (hit) b = bg;
-      }
-      if (!hit) {
-        const int j = lower_bound_guess(A.bts, nb, key + 1, bt0, bstep) - 1;
-        if (j >= 0 && A.bts[j] == key) b = A.bclose[j];
-      }
+      // the last benchmark row with this time (bq_bench_lookup.h: two loads on
+      // a regular grid, the search otherwise)
+      bench_last_match(A.bts, A.bclose, nb, ts[t], bt0, bstep, b);
     }
     sC[i] = c;
     sB[i] = b;

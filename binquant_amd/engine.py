@@ -1376,6 +1376,151 @@ def leadership(open_time: torch.Tensor, close: torch.Tensor, bench_ts: torch.Ten
     return {"leader": leader, "rs_2h": rs2, "rs_6h": rs6}
 
 
+IMPULSE_TILE = _lib.IMPULSE_TILE   # candles per workgroup tile of bq_impulse_rider / bq_bb_stable
+IMPULSE_DEFAULTS = dict(   # RelativeStrengthImpulseRider's class attributes (:36-46)
+    min_history=20, min_impulse=0.05, max_impulse=0.18, min_rs=0.08, max_btc_return=0.01, min_conf_return=0.0,
+    min_close_location=0.70, max_atr_pct=0.06, entry_factor=1 - 1.0 / 100)
+
+
+def _gate_rows(v, name: str, S: int):
+    """lens / first_t: None or S integers (checked before any device work)."""
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        if v.dtype.is_floating_point or v.dtype == torch.bool:
+            raise ValueError(f"{name}: expected an integer tensor, got {v.dtype}")
+        if v.numel() != S:
+            raise ValueError(f"{name}: expected {S} entries, got {v.numel()}")
+        return v
+    v = torch.as_tensor(v, dtype=torch.int64)
+    if v.numel() != S:
+        raise ValueError(f"{name}: expected {S} entries, got {v.numel()}")
+    return v
+
+
+def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
+    """The columns on one row pitch (as given when they share one — e.g. the
+    padded enrich views — else contiguous copies)."""
+    ld = _row_stride(cols[0])
+    if any(_row_stride(c) != ld for c in cols[1:]):
+        cols = [c.contiguous() for c in cols]
+        ld = _row_stride(cols[0])
+    return cols, ld
+
+
+@device_entry
+def impulse_rider(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Tensor, atr: torch.Tensor,
+                  open_time: torch.Tensor, bench_ts: torch.Tensor, bench_close: torch.Tensor, *, first_t=None,
+                  lens=None, columns=_lib.IMPULSE_VALUES, check_bench: bool = True, **thresholds):
+    """RelativeStrengthImpulseRider._features at every prefix t
+    (strategies/relative_strength_impulse_rider.py:92-198; bq_impulse_rider):
+    column t of row s = the method on df.iloc[first_t[s]:t + 1] against the
+    benchmark frame (bench_ts ascending, a repeated time resolves to its last
+    row). Panels [S, T] float64 with unit stride along T and any row pitch,
+    open_time [S, T] int64 ms. Returns (values, status): values maps each name
+    of `columns` (a subset of _lib.IMPULSE_VALUES; others are not computed)
+    to [S, T] float64 — the method's value where status == 0, NaN elsewhere —
+    and status is [S, T] uint8 (_lib.BQ_IR_*; BQ_IR_NO_FRAME where
+    t >= lens[s]). thresholds: IMPULSE_DEFAULTS' keys. check_bench: verify
+    that bench_ts ascends (ValueError otherwise; one small reduction read
+    back to the host, skipped while a graph is being captured) — False for
+    callers that built the benchmark frame themselves."""
+    bad = set(thresholds) - set(IMPULSE_DEFAULTS)
+    if bad:
+        raise ValueError(f"impulse_rider: unknown thresholds {sorted(bad)} (known: {sorted(IMPULSE_DEFAULTS)})")
+    par = {**IMPULSE_DEFAULTS, **thresholds}
+    if int(par["min_history"]) < 7:
+        raise ValueError("impulse_rider: min_history must be >= 7 (the stencil reaches t - 6)")
+    columns = tuple(columns)
+    unknown = [k for k in columns if k not in _lib.IMPULSE_VALUES]
+    if unknown:
+        raise ValueError(f"impulse_rider: unknown columns {unknown}")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    for x, name in ((o, "open"), (h, "high"), (l, "low"), (c, "close"), (atr, "atr")):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
+        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
+    if not isinstance(bench_ts, torch.Tensor) or bench_ts.dtype != torch.int64 or bench_ts.dim() != 1:
+        raise ValueError("bench_ts: expected a 1-D int64 tensor of ms timestamps")
+    if not isinstance(bench_close, torch.Tensor) or bench_close.dtype != torch.float64 \
+            or tuple(bench_close.shape) != tuple(bench_ts.shape):
+        raise ValueError(f"bench_close: expected a float64 tensor of shape {tuple(bench_ts.shape)}")
+    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
+    if not bench_ts.is_cuda and bench_ts.numel() > 1 and bool((bench_ts[1:] < bench_ts[:-1]).any()):
+        raise ValueError("bench_ts: must be ascending")   # a host tensor: rejected without a device
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in ((o, "open"), (h, "high"), (l, "low"),
+                                                                 (c, "close"))])
+    atr = _check_panel(atr, "atr")
+    ts = _check_ts(open_time, "open_time")
+    bts = _check_ts(bench_ts, "bench_ts").reshape(-1)
+    bc = _check_panel(bench_close.reshape(1, -1), "bench_close").contiguous()
+    if check_bench:
+        _check_ascending(bts)
+    dev = c.device
+    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
+    p = _lib.BqImpulseParams()
+    for k in ("min_impulse", "max_impulse", "min_rs", "max_btc_return", "min_conf_return", "min_close_location",
+              "max_atr_pct", "entry_factor"):
+        setattr(p, k, float(par[k]))
+    p.min_history = int(par["min_history"])
+    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
+    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.IMPULSE_VALUES])
+    st = _lib.load().bq_impulse_rider(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), ld_in, _ptr(atr),
+                                      _row_stride(atr), _ptr(ts), T, _ptr(lens), _ptr(first_t), S, T, _ptr(bts),
+                                      _ptr(bc), bts.numel(), ctypes.byref(p), _ptr(status), vals, T,
+                                      _stream_handle(None))
+    _lib.check(st, "bq_impulse_rider")
+    return outs, status
+
+
+def _check_ascending(bts: torch.Tensor) -> None:
+    """bench_ts ascending, else ValueError. One small reduction read back to
+    the host; skipped while a graph is being captured (no host sync there:
+    the captured caller vouches for its benchmark frame)."""
+    if bts.numel() < 2 or torch.cuda.is_current_stream_capturing():
+        return
+    if bool((bts[1:] < bts[:-1]).any()):
+        raise ValueError("bench_ts: must be ascending")
+
+
+@device_entry
+def bb_stable(bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tensor, n: int = 8,
+              max_change_pct: float = 20.0, *, first_t=None, lens=None, change: bool = True):
+    """LadderDeployer._bb_stable(n, max_change_pct) at every prefix t
+    (strategies/grid/ladder_deployer.py:42-56; bq_bb_stable) on
+    df.iloc[first_t[s]:t + 1]. Panels [S, T] float64, unit stride along T,
+    any row pitch. Returns (stable bool [S, T], change_pct [S, T] float64 —
+    NaN where the method returns before computing it — or None with
+    change=False)."""
+    if not 1 <= int(n) <= _lib.BB_STABLE_MAX_N:
+        raise ValueError(f"bb_stable: n must be in 1..{_lib.BB_STABLE_MAX_N}, got {n}")
+    if not isinstance(bb_mid, torch.Tensor) or bb_mid.dim() != 2:
+        raise ValueError("bb_mid: expected [S, T] with unit stride along T")
+    S, T = bb_mid.shape
+    for x, name in ((bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower")):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
+    cols, ld_in = _common_pitch([_check_panel(x, nm) for x, nm in ((bb_upper, "bb_upper"), (bb_mid, "bb_mid"),
+                                                                   (bb_lower, "bb_lower"))])
+    dev = bb_mid.device
+    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
+    stable = torch.empty((S, T), dtype=torch.bool, device=dev)
+    chg = torch.empty((S, T), dtype=torch.float64, device=dev) if change else None
+    st = _lib.load().bq_bb_stable(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ld_in, _ptr(lens), _ptr(first_t), S, T,
+                                  int(n), float(max_change_pct), _ptr(stable), _ptr(chg), T, _stream_handle(None))
+    _lib.check(st, "bq_bb_stable")
+    return stable, chg
+
+
 def _join_capacity(ts: torch.Tensor, lens: torch.Tensor | None, bts: torch.Tensor) -> int:
     """Largest per-row count of (candle, benchmark row) matches over the
     candles t >= 1 that join (bench_ts ascending): an upper bound on every

@@ -17,6 +17,11 @@ prefix frame df.iloc[:t + 1]:
 * top_gainer_features TopGainerEarlyMomentum._features
                      (strategies/top_gainer_early_momentum.py:92-160)
 * mean_reversion_features  the entry inputs of MeanReversionFade (:240-255)
+* impulse_rider_features   RelativeStrengthImpulseRider._features
+                     (strategies/relative_strength_impulse_rider.py:92-198), one
+                     pass (bq_impulse.hip)
+* bb_width_stable    LadderDeployer._bb_stable (strategies/grid/ladder_deployer.py:42-56),
+                     one pass (bq_impulse.hip)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -33,7 +38,7 @@ from __future__ import annotations
 
 import torch
 
-from . import engine
+from . import _lib, engine
 from . import fused as F
 
 NAN = float("nan")
@@ -248,6 +253,71 @@ def gradual_gainer_leadership(open_time: torch.Tensor, close: torch.Tensor, btc_
     leader = strengths & ~F.isnan(T2) & (R2 > 0) & (R6 > 0) & (R2 >= T2) & (R6 >= T6)
     res = F.run({"leader": leader, "rs_2h": F.where(strengths, R2, 0.0), "rs_6h": F.where(strengths, R6, 0.0)}, S, T)
     return res
+
+
+# RelativeStrengthImpulseRider._features reason strings, as uint8 codes
+# (the first failing check in the method's order; bq_impulse_rider's BQ_IR_*)
+(IR_CONFIRMED, IR_SHORT_HISTORY, IR_INVALID_VALUES, IR_INVALID_ANCHORS, IR_BTC_UNAVAILABLE, IR_RANGE_INVALID,
+ IR_NOT_READY, IR_IMPULSE_RANGE, IR_DID_NOT_CROSS, IR_BTC_TOO_HIGH, IR_RS_TOO_LOW, IR_ATR_TOO_HIGH, IR_DID_NOT_HOLD,
+ IR_CONFIRMATION_NEGATIVE, IR_CLOSE_NOT_NEAR_HIGH) = range(15)
+IR_NO_FRAME = _lib.BQ_IR_NO_FRAME   # t >= lens[s]: no such prefix frame (not a reference reason)
+IR_REASONS = {
+    IR_CONFIRMED: "relative_strength_impulse_confirmed",
+    IR_SHORT_HISTORY: "history_too_short",
+    IR_INVALID_VALUES: "invalid_candle_values",
+    IR_INVALID_ANCHORS: "invalid_return_anchors",
+    IR_BTC_UNAVAILABLE: "btc_return_unavailable",
+    IR_RANGE_INVALID: "confirmation_range_invalid",
+    IR_NOT_READY: "indicators_not_ready",
+    IR_IMPULSE_RANGE: "impulse_outside_range",
+    IR_DID_NOT_CROSS: "impulse_did_not_cross_threshold",
+    IR_BTC_TOO_HIGH: "btc_return_too_high",
+    IR_RS_TOO_LOW: "relative_strength_too_low",
+    IR_ATR_TOO_HIGH: "atr_pct_too_high",
+    IR_DID_NOT_HOLD: "confirmation_did_not_hold_trigger_close",
+    IR_CONFIRMATION_NEGATIVE: "confirmation_return_negative",
+    IR_CLOSE_NOT_NEAR_HIGH: "confirmation_close_not_near_high",
+}
+IR_KEYS = _lib.IMPULSE_VALUES
+
+
+def impulse_rider_features(o, h, l, c, atr, open_time, btc_time, btc_close, *, first_t=None, lens=None,
+                           columns=IR_KEYS, check_bench: bool = True, **thresholds):
+    """RelativeStrengthImpulseRider._features evaluated at every t
+    (strategies/relative_strength_impulse_rider.py:92-198): column t = the
+    method on the prefix frame df.iloc[first_t[s]:t + 1] (first_t: the rows
+    Candles.post_process dropped, default 0) against the benchmark frame
+    (btc_time ascending, a repeated time resolves to its last row, as
+    _btc_return_at's backwards scan does, :74-81). atr is the frame's ATR
+    column (e.g. engine.enrich(...)["ATR"]). One pass (engine.impulse_rider,
+    bq_impulse_rider).
+
+    Returns (values, status): values maps IR_KEYS (or the requested subset)
+    to [S, T] float64 — bit for bit the method's value where status ==
+    IR_CONFIRMED, NaN elsewhere (the method returns None there) — and status
+    is [S, T] uint8: the first failing check (IR_* codes, IR_REASONS gives the
+    reference's reason string), IR_NO_FRAME where t >= lens[s]. trigger_close,
+    confirmation_close and the two open times of the method's dict are the
+    caller's own close[t - 1], close[t], open_time[t - 1], open_time[t].
+    thresholds: min_history, min_impulse, max_impulse, min_rs, max_btc_return,
+    min_conf_return, min_close_location, max_atr_pct, entry_factor
+    (1 - RETEST_DISCOUNT_PCT / 100, formed in Python floats)."""
+    return engine.impulse_rider(o, h, l, c, atr, open_time, btc_time, btc_close, first_t=first_t, lens=lens,
+                                columns=columns, check_bench=check_bench, **thresholds)
+
+
+def bb_width_stable(bb_upper, bb_mid, bb_lower, n: int = 8, max_change_pct: float = 20.0, *, first_t=None,
+                    lens=None) -> dict[str, torch.Tensor]:
+    """LadderDeployer._bb_stable(n, max_change_pct) evaluated at every t
+    (strategies/grid/ladder_deployer.py:42-56; the strategy calls it with
+    MIN_BB_WIDTH_STABILITY_CANDLES = 8, MAX_BB_WIDTH_CHANGE_PCT = 20.0) on the
+    prefix frame df.iloc[first_t[s]:t + 1]. Returns {"stable": bool [S, T],
+    "change_pct": float64 [S, T]}: change_pct is abs((w[-1] - w[0]) / w[0]) *
+    100 over the last n widths (upper - lower) / mid where the method reaches
+    it, NaN where it returns earlier (fewer than n rows, a row with mid <= 0
+    or width <= 0). One pass (engine.bb_stable, bq_bb_stable)."""
+    stable, change = engine.bb_stable(bb_upper, bb_mid, bb_lower, n, max_change_pct, first_t=first_t, lens=lens)
+    return {"stable": stable, "change_pct": change}
 
 
 def mean_reversion_features(o, h, l, c, v, atr, rsi_window: int = 14, volume_ma_window: int = 20,

@@ -45,6 +45,10 @@
  *   bq_context_score   <- context_scoring.py:13-114 + signal_context_scorer.py:15-55
  *   bq_cohort_select   <- the portfolio selectors' winner pick
  *                         (liquidation_sweep_pump.py:38-87, gradual_gainer_retest.py:33-70)
+ *   bq_impulse_rider   <- RelativeStrengthImpulseRider._features / _btc_return_at
+ *                         (strategies/relative_strength_impulse_rider.py:69-198)
+ *   bq_bb_stable       <- LadderDeployer._bb_stable
+ *                         (strategies/grid/ladder_deployer.py:42-56)
  *   bq_breadth_partial <- the per-symbol sums/counts of
  *                         LiveMarketContextAccumulator._build_context
  *                         market_regime/live_market_context_accumulator.py:135-163
@@ -312,6 +316,84 @@ int bq_leadership(const int64_t* open_time, int64_t ld_ts, const double* close, 
                   double rs_quantile, int32_t lookback, int32_t min_history, int32_t min_count,
                   int32_t short_bars, int32_t long_bars, void* workspace, size_t workspace_bytes,
                   uint8_t* leader, double* rs_2h, double* rs_6h, int64_t ld_out, void* stream);
+
+/*
+ * RelativeStrengthImpulseRider._features at every prefix t
+ * (strategies/relative_strength_impulse_rider.py:92-198, with _btc_return_at,
+ * :69-90): column t of row s is the method on df.iloc[first:t + 1], first =
+ * first_t[s] (NULL: 0; the rows Candles.post_process dropped), against the
+ * benchmark frame bench_ts [nb] (ascending; a duplicated time resolves to
+ * its last row, as the method's backwards scan does) / bench_close [nb]
+ * (both may be NULL when nb == 0). open / high / low / close [S][ld_in], atr
+ * (the frame's ATR column) [S][ld_atr], open_time [S][ld_ts] int64 ms.
+ * Trigger = candle t - 1, confirmation = candle t; the benchmark return's
+ * anchor is four POSITIONS before the matched row (:85).
+ *
+ * status [S][ld_out] bytes: the first failing check in the method's order
+ * (BQ_IR_*, 0 = relative_strength_impulse_confirmed); BQ_IR_NO_FRAME where
+ * t >= lens[s] (lens NULL: T). values: BQ_IR_NVALUES device pointers
+ * [S][ld_out] in the order below (a NULL entry, or values == NULL, skips the
+ * column), each the method's own expression (bit-exact) where status is 0
+ * and NaN elsewhere (the method returns None there). params NULL: the class
+ * attributes (bq_impulse_default_params). BQ_EINVAL for min_history < 7 (the
+ * stencil reaches t - 6). No workspace, nothing allocated.
+ */
+#define BQ_IMPULSE_TILE 1024   /* candles per workgroup tile of both kernels */
+#define BQ_IR_CONFIRMED              0   /* :197 */
+#define BQ_IR_SHORT_HISTORY          1   /* history_too_short (:99) */
+#define BQ_IR_INVALID_VALUES         2   /* invalid_candle_values (:124) */
+#define BQ_IR_INVALID_ANCHORS        3   /* invalid_return_anchors (:130) */
+#define BQ_IR_BTC_UNAVAILABLE        4   /* btc_return_unavailable (:137) */
+#define BQ_IR_RANGE_INVALID          5   /* confirmation_range_invalid (:144) */
+#define BQ_IR_NOT_READY              6   /* indicators_not_ready (:159) */
+#define BQ_IR_IMPULSE_RANGE          7   /* impulse_outside_range (:161) */
+#define BQ_IR_DID_NOT_CROSS          8   /* impulse_did_not_cross_threshold (:165) */
+#define BQ_IR_BTC_TOO_HIGH           9   /* btc_return_too_high (:167) */
+#define BQ_IR_RS_TOO_LOW            10   /* relative_strength_too_low (:169) */
+#define BQ_IR_ATR_TOO_HIGH          11   /* atr_pct_too_high (:171) */
+#define BQ_IR_DID_NOT_HOLD          12   /* confirmation_did_not_hold_trigger_close (:173) */
+#define BQ_IR_CONFIRMATION_NEGATIVE 13   /* confirmation_return_negative (:175) */
+#define BQ_IR_CLOSE_NOT_NEAR_HIGH   14   /* confirmation_close_not_near_high (:177) */
+#define BQ_IR_NO_FRAME             255   /* t >= lens[s]: no such prefix frame */
+/* value columns: impulse_return_1h, previous_impulse_return_1h, btc_return_1h,
+ * relative_strength_1h, trigger_return_15m, confirmation_return_15m,
+ * confirmation_close_location, atr_pct, entry_limit_price (:187-195) */
+#define BQ_IR_NVALUES 9
+typedef struct bq_impulse_params {
+  double min_impulse;          /* MIN_IMPULSE_RETURN_1H 0.05 */
+  double max_impulse;          /* MAX_IMPULSE_RETURN_1H 0.18 */
+  double min_rs;               /* MIN_RELATIVE_STRENGTH_1H 0.08 */
+  double max_btc_return;       /* MAX_BTC_RETURN_1H 0.01 */
+  double min_conf_return;      /* MIN_CONFIRMATION_RETURN 0.0 */
+  double min_close_location;   /* MIN_CONFIRMATION_CLOSE_LOCATION 0.70 */
+  double max_atr_pct;          /* MAX_ATR_PCT 0.06 */
+  double entry_factor;         /* 1 - RETEST_DISCOUNT_PCT / 100, formed by the caller in fp64 */
+  int32_t min_history;         /* MIN_HISTORY 20 (>= 7) */
+  int32_t reserved;
+} bq_impulse_params;
+void bq_impulse_default_params(bq_impulse_params* p);
+int bq_impulse_rider(const double* open, const double* high, const double* low, const double* close,
+                     int64_t ld_in, const double* atr, int64_t ld_atr, const int64_t* open_time,
+                     int64_t ld_ts, const int64_t* lens, const int64_t* first_t, int64_t S, int64_t T,
+                     const int64_t* bench_ts, const double* bench_close, int64_t nb,
+                     const bq_impulse_params* params, uint8_t* status, double* const* values,
+                     int64_t ld_out, void* stream);
+
+/*
+ * LadderDeployer._bb_stable(n, max_change_pct) at every prefix t
+ * (strategies/grid/ladder_deployer.py:42-56) on df.iloc[first:t + 1]:
+ * bb_upper / bb_mid / bb_lower [S][ld_in], 1 <= n <= BQ_BB_STABLE_MAX_N
+ * (the strategy: 8, 20.0). stable [S][ld_out] (0 / 1 bytes): at least n rows,
+ * each of the last n with bb_mid > 0 and width = (upper - lower) / mid > 0
+ * (a NaN row passes both tests, as in Python), and
+ * abs((w[t] - w[t-n+1]) / w[t-n+1]) * 100 <= max_change_pct. change_pct
+ * [S][ld_out] (NULL = skip): that expression (bit-exact) where the method
+ * reaches it, NaN where it returns earlier. Columns t >= lens[s]: 0 / NaN.
+ */
+#define BQ_BB_STABLE_MAX_N 64
+int bq_bb_stable(const double* bb_upper, const double* bb_mid, const double* bb_lower, int64_t ld_in,
+                 const int64_t* lens, const int64_t* first_t, int64_t S, int64_t T, int32_t n,
+                 double max_change_pct, uint8_t* stable, double* change_pct, int64_t ld_out, void* stream);
 
 /* ---- benchmark-relative statistics ---------------------------------------- */
 /*
