@@ -30,7 +30,14 @@ $(LIB): $(OBJS)
 resource-usage: $(SRCS)
 	@for f in $(SRCS); do $(HIPCC) $(HIPFLAGS) -c $$f -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "remark" ; done
 
+# one line per kernel file: SHA-256 of its gfx950 device assembly text. The
+# __hip_cuid_* symbol hashes the source text, so its lines are dropped; equal
+# digests before and after a refactor mean the device code did not change.
+isa-digest: $(SRCS)
+	@for f in $(SRCS); do printf '%s  ' $$(basename $$f); \
+	  $(HIPCC) $(HIPFLAGS) --cuda-device-only -S $$f -o - | grep -v __hip_cuid | sha256sum | cut -d' ' -f1 ; done
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean resource-usage
+.PHONY: all clean resource-usage isa-digest

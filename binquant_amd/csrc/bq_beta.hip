@@ -29,24 +29,17 @@
 // covariance / NaN correlation. The previous candle of lane 0 and the run /
 // total carries come from the previous tile through readlane; the next tile's
 // prices are in flight while the current one computes.
-#include "bq_device.h"
+#include "bq_rowtile.h"
 #include "binquant_amd.h"
 
 #include <string.h>
 
 namespace bq {
 
-constexpr int BC_NT = 256;   // beta_btc_stats_kernel block
-constexpr int BC_NW = BC_NT / WAVE;
-constexpr int BC_K = 4;      // candles per lane
-constexpr int BC_TT = BC_NT * BC_K;
-constexpr int BC_H = 128;
-constexpr int BC_R = BC_H + BC_TT;
-constexpr int BC_Q = BC_R / BC_K;
-static_assert(BC_R % BC_K == 0 && BC_H >= BQ_MAX_WINDOW + 2, "ring shape");
-// ring position -> slot, lane-interleaved (in the natural layout the lanes'
-// candles are K apart: multi-way bank conflicts on every access)
-__device__ __forceinline__ int bslot(int p) { return (p % BC_K) * BC_Q + p / BC_K; }
+// beta_btc_stats_kernel's block: 256 threads, 4 candles per lane; the halo
+// holds a whole window of prefixes (the wave kernel shares K and H)
+using BC = RowTile<256, 4, 128>;
+static_assert(BC::H >= BQ_MAX_WINDOW + 2, "ring shape");
 
 struct BetaArgs {
   const double* close;   // PAIRS: symbol returns
@@ -81,38 +74,18 @@ __device__ __forceinline__ double wave_scan_f64(double x, int lane) {
   return x + c;
 }
 
-// A lane's 4 consecutive candles: two 16-byte accesses where the row allows
-// (each instruction then fills half of every line it touches instead of a
-// quarter; nontemporal loads measured slower here, nontemporal stores faster).
-typedef double bq_v2d __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void ld4(const double* __restrict__ r, int t, int T, bool vec, double (&v)[4]) {
-  if (vec && t + 4 <= T) {
-    const bq_v2d* p = reinterpret_cast<const bq_v2d*>(r + t);
-    const bq_v2d a = p[0], b = p[1];
-    v[0] = a.x;
-    v[1] = a.y;
-    v[2] = b.x;
-    v[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = t + k < T ? r[t + k] : qnan();
-  }
-}
-
-// write-once outputs: whole-line nontemporal stores (bq_device.h store_lines);
-// the wave's lanes all call it (one wave per symbol)
-__device__ __forceinline__ void st4(double* r, int t, int T, bool vec, const double (&v)[4]) {
-  store_lines<4>(r, t, T, vec, v);
-}
-
-constexpr int BW_TT = WAVE * BC_K;   // candles per tile
+// A lane's 4 consecutive candles are two 16-byte accesses where the row allows
+// (load_lane; each instruction then fills half of every line it touches
+// instead of a quarter; nontemporal loads measured slower here, nontemporal
+// stores faster: store_lines, which the wave's lanes all call).
+constexpr int BW_TT = WAVE * BC::K;   // candles per tile
 constexpr int BW_R = 512;            // ring: a tile plus a halo of up to 256 candles
-constexpr int BW_Q = BW_R / BC_K;
-static_assert(BW_R >= BW_TT + BC_H && (BW_R & (BW_R - 1)) == 0 && BC_K == 4, "wave ring shape");
+constexpr int BW_Q = BW_R / BC::K;
+static_assert(BW_R >= BW_TT + BC::H && (BW_R & (BW_R - 1)) == 0 && BC::K == 4, "wave ring shape");
 // candle index (negative: before the row) -> ring slot, lane-interleaved
 __device__ __forceinline__ int wslot(int t) {
   const unsigned p = (unsigned)t & (BW_R - 1);
-  return (int)((p & (BC_K - 1)) * BW_Q + (p >> 2));
+  return (int)((p & (BC::K - 1)) * BW_Q + (p >> 2));
 }
 #ifndef BQ_BW_WAVES
 #define BQ_BW_WAVES 3   // waves per SIMD the MODE 3 register budget is cut for
@@ -148,53 +121,53 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
   }
   // empty prefixes before the row (the halo of the first tile)
 #pragma unroll
-  for (int h = 0; h < BC_H; h += WAVE)
+  for (int h = 0; h < BC::H; h += WAVE)
 #pragma unroll
-    for (int s2 = 0; s2 < NS; ++s2) sP[s2][wslot(h + lane - BC_H)] = 0.0;
+    for (int s2 = 0; s2 < NS; ++s2) sP[s2][wslot(h + lane - BC::H)] = 0.0;
   // carries of the previous tile (wave-uniform)
   double cprev = qnan(), bprev = qnan(), xprev = qnan(), yprev = qnan(), xyprev = qnan();
   int carx = -1, cary = -1, carxy = -1;
   const bool vin = A.vin, vbtc = A.vbtc, vout = A.vout;
-  double cn[BC_K], bn[BC_K];
-  ld4(rc, BC_K * lane, T, vin, cn);
-  ld4(rb, BC_K * lane, T, vbtc, bn);
+  double cn[BC::K], bn[BC::K];
+  load_lane<BC::K>(rc, BC::K * lane, T, vin, cn);
+  load_lane<BC::K>(rb, BC::K * lane, T, vbtc, bn);
   const double wd = (double)win;
   for (int t0 = 0; t0 < T; t0 += BW_TT) {
-    const int tb = t0 + BC_K * lane;
+    const int tb = t0 + BC::K * lane;
     // MODE 3: the benchmark's window stats of this tile (L2 hits: every symbol
     // reads the same rows), issued before the next tile's prefetch so that
     // waiting for them does not wait for it (loads retire in order)
-    double ym[BC_K], yv[BC_K], yi[BC_K];
+    double ym[BC::K], yv[BC::K], yi[BC::K];
     if (YST) {
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) {
+      for (int k = 0; k < BC::K; ++k) {
         const bool ok = tb + k < T;
         ym[k] = ok ? A.ystat[tb + k] : 0.0;
         yv[k] = ok ? A.ystat[T + tb + k] : 0.0;
         yi[k] = ok ? A.ystat[2 * T + tb + k] : 0.0;
       }
     }
-    double x[BC_K], y[BC_K];
+    double x[BC::K], y[BC::K];
     {
-      double c[BC_K], b[BC_K];
+      double c[BC::K], b[BC::K];
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) {
+      for (int k = 0; k < BC::K; ++k) {
         c[k] = cn[k];
         b[k] = bn[k];
       }
       if (t0 + BW_TT < T) {   // next tile's inputs in flight during this one
-        ld4(rc, tb + BW_TT, T, vin, cn);
-        ld4(rb, tb + BW_TT, T, vbtc, bn);
+        load_lane<BC::K>(rc, tb + BW_TT, T, vin, cn);
+        load_lane<BC::K>(rb, tb + BW_TT, T, vbtc, bn);
       }
-      double pc = dpp_f64<DPP_WAVE_SHR1>(c[BC_K - 1]), pbt = dpp_f64<DPP_WAVE_SHR1>(b[BC_K - 1]);
+      double pc = dpp_f64<DPP_WAVE_SHR1>(c[BC::K - 1]), pbt = dpp_f64<DPP_WAVE_SHR1>(b[BC::K - 1]);
       if (lane == 0) {
         pc = cprev;
         pbt = bprev;
       }
-      cprev = readlane_f64(c[BC_K - 1], WAVE - 1);
-      if (!BRET) bprev = readlane_f64(b[BC_K - 1], WAVE - 1);
+      cprev = readlane_f64(c[BC::K - 1], WAVE - 1);
+      if (!BRET) bprev = readlane_f64(b[BC::K - 1], WAVE - 1);
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) {
+      for (int k = 0; k < BC::K; ++k) {
         if (PAIRS) {
           x[k] = c[k];
           y[k] = b[k];
@@ -209,14 +182,14 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
     // per-candle terms (a candle without both returns adds nothing), their
     // tile-local inclusive prefixes, and the last index where x / y / x*y
     // changed (the same-value rule)
-    double q[NS][BC_K];
-    int lcx[BC_K], lcy[BC_K], lcxy[BC_K];
+    double q[NS][BC::K];
+    int lcx[BC::K], lcy[BC::K], lcxy[BC::K];
     {
       double acc[NS];
 #pragma unroll
       for (int s2 = 0; s2 < NS; ++s2) acc[s2] = 0.0;
-      double px = dpp_f64<DPP_WAVE_SHR1>(x[BC_K - 1]), py = dpp_f64<DPP_WAVE_SHR1>(y[BC_K - 1]);
-      double pxy = dpp_f64<DPP_WAVE_SHR1>(x[BC_K - 1] * y[BC_K - 1]);
+      double px = dpp_f64<DPP_WAVE_SHR1>(x[BC::K - 1]), py = dpp_f64<DPP_WAVE_SHR1>(y[BC::K - 1]);
+      double pxy = dpp_f64<DPP_WAVE_SHR1>(x[BC::K - 1] * y[BC::K - 1]);
       if (lane == 0) {
         px = xprev;
         py = yprev;
@@ -224,7 +197,7 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
       }
       int lx = -1, ly = -1, lxy = -1;
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) {
+      for (int k = 0; k < BC::K; ++k) {
         const int t = tb + k;
         const bool ok = x[k] == x[k] && y[k] == y[k];
         const double xy = x[k] * y[k];
@@ -251,14 +224,14 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
         py = y[k];
         pxy = xy;
       }
-      xprev = readlane_f64(x[BC_K - 1], WAVE - 1);
-      if (!YST) yprev = readlane_f64(y[BC_K - 1], WAVE - 1);
-      xyprev = readlane_f64(x[BC_K - 1] * y[BC_K - 1], WAVE - 1);
+      xprev = readlane_f64(x[BC::K - 1], WAVE - 1);
+      if (!YST) yprev = readlane_f64(y[BC::K - 1], WAVE - 1);
+      xyprev = readlane_f64(x[BC::K - 1] * y[BC::K - 1], WAVE - 1);
 #pragma unroll
       for (int s2 = 0; s2 < NS; ++s2) {
         const double ex = wave_scan_f64(acc[s2], lane) - acc[s2];
 #pragma unroll
-        for (int k = 0; k < BC_K; ++k) q[s2][k] += ex;
+        for (int k = 0; k < BC::K; ++k) q[s2][k] += ex;
       }
       const int ix = wave_scan_max_dpp(lx + 1, lane) - 1, iy = YST ? -1 : wave_scan_max_dpp(ly + 1, lane) - 1,
                 ixy = wave_scan_max_dpp(lxy + 1, lane) - 1;
@@ -266,7 +239,7 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
                 cy = YST ? -1 : max(cary, dpp_i32<DPP_WAVE_SHR1>(iy + 1) - 1),
                 cxy = max(carxy, dpp_i32<DPP_WAVE_SHR1>(ixy + 1) - 1);
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) {
+      for (int k = 0; k < BC::K; ++k) {
         lcx[k] = max(lcx[k], cx);
         lcy[k] = max(lcy[k], cy);
         lcxy[k] = max(lcxy[k], cxy);
@@ -275,9 +248,9 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
       }
     }
     __syncthreads();   // one wave: orders the ring writes before the reads
-    double beta[BC_K], corr[BC_K];
+    double beta[BC::K], corr[BC::K];
 #pragma unroll
-    for (int k = 0; k < BC_K; ++k) {
+    for (int k = 0; k < BC::K; ++k) {
       const int t = tb + k;
       // (computed for every lane, the incomplete windows masked at the end:
       // a ring read before the row start is a zeroed slot)
@@ -316,21 +289,21 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
       corr[k] = full ? cov * rsq_nr(vx * vy) : qnan();
     }
     const int64_t orow = sym * A.ld_out;
-    if (A.beta) st4(A.beta + orow, tb, T, vout, beta);
-    if (A.corr) st4(A.corr + orow, tb, T, vout, corr);
-    carx = __builtin_amdgcn_readlane(lcx[BC_K - 1], WAVE - 1);
-    cary = __builtin_amdgcn_readlane(lcy[BC_K - 1], WAVE - 1);
-    carxy = __builtin_amdgcn_readlane(lcxy[BC_K - 1], WAVE - 1);
+    if (A.beta) store_lines<BC::K>(A.beta + orow, tb, T, vout, beta);
+    if (A.corr) store_lines<BC::K>(A.corr + orow, tb, T, vout, corr);
+    carx = __builtin_amdgcn_readlane(lcx[BC::K - 1], WAVE - 1);
+    cary = __builtin_amdgcn_readlane(lcy[BC::K - 1], WAVE - 1);
+    carxy = __builtin_amdgcn_readlane(lcxy[BC::K - 1], WAVE - 1);
     if (t0 + BW_TT >= T) break;
     // the halo of the next tile: this tile's last 128 prefixes in the next
     // tile's frame (held in registers by lanes 32..63)
     double tot[NS];
 #pragma unroll
-    for (int s2 = 0; s2 < NS; ++s2) tot[s2] = readlane_f64(q[s2][BC_K - 1], WAVE - 1);
+    for (int s2 = 0; s2 < NS; ++s2) tot[s2] = readlane_f64(q[s2][BC::K - 1], WAVE - 1);
     __syncthreads();   // this tile's ring reads are done
-    if (BC_K * lane >= BW_TT - BC_H) {
+    if (BC::K * lane >= BW_TT - BC::H) {
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k)
+      for (int k = 0; k < BC::K; ++k)
 #pragma unroll
         for (int s2 = 0; s2 < NS; ++s2) sP[s2][wslot(tb + k)] = q[s2][k] - tot[s2];
     }
@@ -347,12 +320,12 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
 // bp != NULL: y is formed here from the benchmark's prices
 // (log_return(bp[t], bp[t-1]), NaN at t = 0) and written to ystat[3][t] for
 // the symbol walk, so a call needs no separate returns pass.
-__global__ __launch_bounds__(BC_NT) void beta_btc_stats_kernel(const double* __restrict__ y,
+__global__ __launch_bounds__(BC::NT) void beta_btc_stats_kernel(const double* __restrict__ y,
                                                                const double* __restrict__ bp, int T, int win,
                                                                double inv_w, double inv_w1, double* ystat) {
-  __shared__ double sP[2][BC_R];
-  __shared__ double sWt[2][BC_NW];
-  __shared__ int sWl[BC_NW];
+  __shared__ double sP[2][BC::R];
+  __shared__ double sWt[2][BC::NW];
+  __shared__ int sWl[BC::NW];
   __shared__ int sCar;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
   const auto yv = [&](int t) -> double {
@@ -362,15 +335,15 @@ __global__ __launch_bounds__(BC_NT) void beta_btc_stats_kernel(const double* __r
   };
   double ry = T > 1 ? yv(1) : 0.0;
   if (ry != ry) ry = 0.0;
-  if (tid < BC_H) sP[0][bslot(tid)] = sP[1][bslot(tid)] = 0.0;
+  if (tid < BC::H) sP[0][BC::slot(tid)] = sP[1][BC::slot(tid)] = 0.0;
   if (tid == 0) sCar = -1;
-  for (int t0 = 0; t0 < T; t0 += BC_TT) {
-    const int tb = t0 + BC_K * tid, pb = BC_H + BC_K * tid;
-    double v[BC_K], q[2][BC_K], acc[2] = {0.0, 0.0};
-    int lc[BC_K], l = -1;
+  for (int t0 = 0; t0 < T; t0 += BC::TT) {
+    const int tb = t0 + BC::K * tid, pb = BC::H + BC::K * tid;
+    double v[BC::K], q[2][BC::K], acc[2] = {0.0, 0.0};
+    int lc[BC::K], l = -1;
     double pv = tb >= 1 && tb <= T ? yv(tb - 1) : qnan();
 #pragma unroll
-    for (int k = 0; k < BC_K; ++k) {
+    for (int k = 0; k < BC::K; ++k) {
       const int t = tb + k;
       v[k] = yv(t);
       if (bp && t < T) ystat[3 * T + t] = v[k];
@@ -390,32 +363,27 @@ __global__ __launch_bounds__(BC_NT) void beta_btc_stats_kernel(const double* __r
       const double inc = wave_scan_f64(acc[s2], lane);
       if (lane == WAVE - 1) sWt[s2][w] = inc;
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) q[s2][k] += inc - acc[s2];
+      for (int k = 0; k < BC::K; ++k) q[s2][k] += inc - acc[s2];
     }
-    const int il = wave_scan_max_dpp(l + 1, lane) - 1;
-    if (lane == WAVE - 1) sWl[w] = il;
-    const int exl = dpp_i32<DPP_WAVE_SHR1>(il + 1) - 1;
-    __syncthreads();
-    int c = max(sCar, exl);
+    const int c = block_excl_max(l, &sCar, sWl, lane, w);   // its barrier also publishes sWt
     double base[2] = {0.0, 0.0};
     for (int u = 0; u < w; ++u) {
-      c = max(c, sWl[u]);
       base[0] += sWt[0][u];
       base[1] += sWt[1][u];
     }
 #pragma unroll
-    for (int k = 0; k < BC_K; ++k) {
+    for (int k = 0; k < BC::K; ++k) {
       lc[k] = max(lc[k], c);
       q[0][k] += base[0];
       q[1][k] += base[1];
-      sP[0][bslot(pb + k)] = q[0][k];
-      sP[1][bslot(pb + k)] = q[1][k];
+      sP[0][BC::slot(pb + k)] = q[0][k];
+      sP[1][BC::slot(pb + k)] = q[1][k];
     }
     __syncthreads();
     const double wd = (double)win;
 #pragma unroll
-    for (int k = 0; k < BC_K; ++k) {
-      const int t = tb + k, o = bslot(pb + k - win);
+    for (int k = 0; k < BC::K; ++k) {
+      const int t = tb + k, o = BC::slot(pb + k - win);
       if (t >= T) continue;
       double m = qnan(), var = qnan();
       if (t >= win) {
@@ -434,17 +402,17 @@ __global__ __launch_bounds__(BC_NT) void beta_btc_stats_kernel(const double* __r
       ystat[T + t] = var;
       ystat[2 * T + t] = var == 0.0 ? qnan() : 1.0 / var;
     }
-    if (t0 + BC_TT >= T) break;
-    double last[2] = {sP[0][bslot(BC_R - 1)], sP[1][bslot(BC_R - 1)]};
+    if (t0 + BC::TT >= T) break;
+    double last[2] = {sP[0][BC::slot(BC::R - 1)], sP[1][BC::slot(BC::R - 1)]};
     __syncthreads();
-    if (pb >= BC_TT) {
+    if (pb >= BC::TT) {
 #pragma unroll
-      for (int k = 0; k < BC_K; ++k) {
-        sP[0][bslot(pb + k - BC_TT)] = q[0][k] - last[0];
-        sP[1][bslot(pb + k - BC_TT)] = q[1][k] - last[1];
+      for (int k = 0; k < BC::K; ++k) {
+        sP[0][BC::slot(pb + k - BC::TT)] = q[0][k] - last[0];
+        sP[1][BC::slot(pb + k - BC::TT)] = q[1][k] - last[1];
       }
     }
-    if (tid == BC_NT - 1) sCar = lc[BC_K - 1];
+    if (tid == BC::NT - 1) sCar = lc[BC::K - 1];
   }
 }
 
@@ -472,12 +440,12 @@ int launch_beta(int mode, const double* close, const double* btc_close, int64_t 
   A.inv_w1 = 1.0 / (double)(window - 1);
   A.bias = (double)window / (double)(window - 1);
   A.ystat = ystat;
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  A.vin = a16(close) && (ld_in & 1) == 0;
-  A.vbtc = (mode == 4 ? a16(ystat + 3 * T) : a16(btc_close)) && (mode != 1 || (ld_in & 1) == 0);
-  A.vout = (!beta || a16(beta)) && (!corr || a16(corr)) && (ld_out & 1) == 0;
+  const double* const outs[2] = {beta, corr};
+  A.vin = vec_row(close, ld_in);
+  A.vbtc = aligned16(mode == 4 ? ystat + 3 * T : btc_close) && (mode != 1 || (ld_in & 1) == 0);
+  A.vout = vec_rows(outs, 2, ld_out);
   if (mode == 3 || mode == 4) {   // 4: benchmark prices, its returns formed by the pre-pass into ystat[3]
-    hipLaunchKernelGGL(beta_btc_stats_kernel, dim3(1), dim3(BC_NT), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(beta_btc_stats_kernel, dim3(1), dim3(BC::NT), 0, (hipStream_t)stream,
                        mode == 3 ? btc_close : nullptr, mode == 4 ? btc_close : nullptr, A.T, window, A.inv_w,
                        A.inv_w1, ystat);
     if (mode == 4) A.btc = ystat + 3 * T;

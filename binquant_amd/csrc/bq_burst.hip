@@ -20,7 +20,7 @@
 // pipeline bit for bit. One thread = 4 consecutive candles of a row (16-byte
 // loads, whole-line stores, 4-byte flag stores); the few look-back values
 // (close t-1 .. t-3, raw t-3 .. t-1) are re-read from L1 / L2.
-#include "bq_device.h"
+#include "bq_rowtile.h"
 #include "binquant_amd.h"
 
 #include <stdint.h>
@@ -44,34 +44,6 @@ struct BurstArgs {
   double mb, vol_mult, qv_mult, price_thr, min_range, min_body, max_cth;
 };
 
-typedef double bu_dbl2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void bu_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[BU_K]) {
-  if (vec && tb + BU_K <= T) {
-    const bu_dbl2* p = reinterpret_cast<const bu_dbl2*>(row + tb);
-    const bu_dbl2 a = p[0], b = p[1];
-    x[0] = a.x;
-    x[1] = a.y;
-    x[2] = b.x;
-    x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < BU_K; ++k) x[k] = tb + k < T ? row[tb + k] : qnan();
-  }
-}
-
-// 4 flags of consecutive candles: one 4-byte store when the row offset allows
-__device__ __forceinline__ void bu_put_bytes(uint8_t* __restrict__ row, int tb, int T, bool vec4, const bool (&b)[BU_K]) {
-  if (vec4 && tb + BU_K <= T) {
-    const uint32_t w = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-    *reinterpret_cast<uint32_t*>(row + tb) = w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < BU_K; ++k)
-      if (tb + k < T) row[tb + k] = b[k] ? 1 : 0;
-  }
-}
-
 __device__ __forceinline__ double clip_lo(double x, double lo) { return x < lo ? lo : x; }   // NaN stays
 
 __global__ __launch_bounds__(BU_NT) void burst_features_kernel(const BurstArgs A, int vin, int vout, int vb) {
@@ -81,15 +53,15 @@ __global__ __launch_bounds__(BU_NT) void burst_features_kernel(const BurstArgs A
   const int64_t irow = sym * A.ld_in, orow = sym * A.ld_out;
   const bool hq = A.has_q != 0;
   double o[BU_K], h[BU_K], l[BU_K], c[BU_K], v[BU_K], q[BU_K], mv[BU_K], mq[BU_K];
-  bu_load(A.in[BU_O] + irow, tb, T, vin, o);
-  bu_load(A.in[BU_H] + irow, tb, T, vin, h);
-  bu_load(A.in[BU_L] + irow, tb, T, vin, l);
-  bu_load(A.in[BU_C] + irow, tb, T, vin, c);
-  bu_load(A.in[BU_V] + irow, tb, T, vin, v);
-  bu_load(A.in[BU_MEDV] + irow, tb, T, vin, mv);
+  load_lane<BU_K>(A.in[BU_O] + irow, tb, T, vin, o);
+  load_lane<BU_K>(A.in[BU_H] + irow, tb, T, vin, h);
+  load_lane<BU_K>(A.in[BU_L] + irow, tb, T, vin, l);
+  load_lane<BU_K>(A.in[BU_C] + irow, tb, T, vin, c);
+  load_lane<BU_K>(A.in[BU_V] + irow, tb, T, vin, v);
+  load_lane<BU_K>(A.in[BU_MEDV] + irow, tb, T, vin, mv);
   if (hq) {
-    bu_load(A.in[BU_Q] + irow, tb, T, vin, q);
-    bu_load(A.in[BU_MEDQ] + irow, tb, T, vin, mq);
+    load_lane<BU_K>(A.in[BU_Q] + irow, tb, T, vin, q);
+    load_lane<BU_K>(A.in[BU_MEDQ] + irow, tb, T, vin, mq);
   }
   // close t-3 .. t-1 of the first candle (NaN before the row)
   double cp[BU_K + 3];
@@ -106,7 +78,7 @@ __global__ __launch_bounds__(BU_NT) void burst_features_kernel(const BurstArgs A
     if (A.out[col]) store_lines<BU_K>(A.out[col] + orow, tb, T, vo, r, whole);
   };
   auto putb = [&](int col, const bool (&b)[BU_K]) {
-    if (A.flag[col]) bu_put_bytes(A.flag[col] + orow, tb, T, v4, b);
+    if (A.flag[col]) put_bytes<BU_K>(A.flag[col] + orow, tb, T, v4, b);
   };
   double bvs[BU_K], vr[BU_K], bqs[BU_K], qvr[BU_K], pj[BU_K], rf[BU_K], bf[BU_K], cth[BU_K], ruc[BU_K], sc[BU_K];
   bool bull[BU_K], vsp[BU_K], qsp[BU_K], pjf[BU_K], ref[BU_K], bqf[BU_K], tqf[BU_K], all[BU_K];
@@ -156,7 +128,7 @@ __global__ __launch_bounds__(BU_NT) void burst_features_kernel(const BurstArgs A
   putb(BQ_BURST_RANGE_EXPANSION_FLAG, ref);
   putb(BQ_BURST_BODY_QUALITY_FLAG, bqf);
   putb(BQ_BURST_TREND_QUALITY_FLAG, tqf);
-  if (A.all) bu_put_bytes(A.all + orow, tb, T, v4, all);
+  if (A.all) put_bytes<BU_K>(A.all + orow, tb, T, v4, all);
 }
 
 struct QualifyArgs {
@@ -193,7 +165,7 @@ __global__ __launch_bounds__(BU_NT) void burst_qualify_kernel(const QualifyArgs 
     for (int j = 0; j < MAXCD; ++j) recent |= j >= MAXCD - CD && r[k + j];
     q[k] = r[MAXCD + k] & !recent;
   }
-  bu_put_bytes(A.out + sym * A.ld_b, tb, T, vb != 0, q);
+  put_bytes<BU_K>(A.out + sym * A.ld_b, tb, T, vb != 0, q);
 }
 
 }  // namespace bq
@@ -230,15 +202,8 @@ extern "C" int bq_burst_features(const double* const* in, int64_t S, int64_t T, 
   A.min_range = p->min_range_frac;
   A.min_body = p->min_body_frac;
   A.max_cth = p->max_close_to_high;
-  auto aligned = [](const void* q, unsigned a) { return (((uintptr_t)q) & (a - 1)) == 0; };
-  int vin = (ld_in % 2) == 0, vout = (ld_out % 2) == 0, vb = (ld_out % 4) == 0;
-  for (int f = 0; f < BU_NIN; ++f)
-    if (in[f]) vin &= aligned(in[f], 16);
-  for (int c = 0; c < BQ_NUM_BURST_F; ++c)
-    if (out_f[c]) vout &= aligned(out_f[c], 16);
-  for (int c = 0; c < BQ_NUM_BURST_B; ++c)
-    if (out_b[c]) vb &= aligned(out_b[c], 4);
-  if (all_flags) vb &= aligned(all_flags, 4);
+  const int vin = vec_rows(in, BU_NIN, ld_in), vout = vec_rows(out_f, BQ_NUM_BURST_F, ld_out);
+  const int vb = vec_bytes(out_b, BQ_NUM_BURST_B, ld_out) && vec_bytes(&all_flags, 1, ld_out);
   const dim3 grid((unsigned)(S * ((T + BU_TT - 1) / BU_TT)));
   hipLaunchKernelGGL(burst_features_kernel, grid, dim3(BU_NT), 0, (hipStream_t)stream, A, vin, vout, vb);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
@@ -261,7 +226,7 @@ extern "C" int bq_burst_qualify(const double* score, const double* threshold, co
   A.ld_b = ld_b;
   A.T = (int)T;
   A.cooldown = cooldown_bars;
-  const int vb = (ld_b % 4) == 0 && (((uintptr_t)qualified) & 3u) == 0;
+  const int vb = vec_bytes(&qualified, 1, ld_b);
   const dim3 grid((unsigned)(S * ((T + BU_TT - 1) / BU_TT)));
   hipLaunchKernelGGL(burst_qualify_kernel, grid, dim3(BU_NT), 0, (hipStream_t)stream, A, vb);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;

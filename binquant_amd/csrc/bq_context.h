@@ -1,11 +1,12 @@
 // What the market-context kernels share (bq_market.hip, bq_context.hip,
 // bq_fresh.hip): the EMA 20 / 50 constants of _compute_symbol_features, the
-// 16-byte alignment rule of the vector paths and the four-candle row load.
+// vector type of the four-candle row load (the load itself and the 16-byte
+// alignment rule of the vector paths: bq_rowtile.h).
 // Internal to the library.
 #pragma once
 #include <stdint.h>
 
-#include "bq_device.h"
+#include "bq_rowtile.h"
 
 namespace bq {
 
@@ -42,30 +43,13 @@ inline FeatEma feat_ema_consts(int max_bars) {
   return E;
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
-
-// the 16-byte vector path over n rows-of-doubles arrays of one stride: an even
-// stride and every given (non-null) base aligned
-inline int vec_rows(const double* const* p, int n, int64_t ld) {
-  bool v = (ld % 2) == 0;
-  for (int i = 0; i < n; ++i) v = v && (!p[i] || aligned16(p[i]));
-  return v;
-}
-
-// candles tb .. tb + 3 of a row; past T, 0.0 or (NAN_PAD) NaN. V2: the 16-byte
-// vector type of the aligned path (each kernel keeps the one it was compiled
-// with); the pad is a template flag because a pad argument moved
+// candles tb .. tb + 3 of a row (load_lane); past T, 0.0 or (NAN_PAD) NaN. V2:
+// the 16-byte vector type of the aligned path (each kernel keeps the one it
+// was compiled with); the pad is a template flag because a pad argument moved
 // panel_compact_kernel's instruction schedule
 template <typename V2, bool NAN_PAD = false>
 __device__ __forceinline__ void load4(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[CTX_K]) {
-  if (vec && tb + CTX_K <= T) {
-    const V2* p = reinterpret_cast<const V2*>(row + tb);
-    const V2 a = p[0], b = p[1];
-    x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < CTX_K; ++k) x[k] = (tb + k < T) ? row[tb + k] : (NAN_PAD ? qnan() : 0.0);
-  }
+  load_lane<CTX_K, NAN_PAD, V2>(row, tb, T, vec, x);
 }
 
 }  // namespace bq

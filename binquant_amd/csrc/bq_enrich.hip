@@ -30,7 +30,7 @@
 //     ewm(adjust=False) update, so per-element rounding follows pandas.
 // HBM traffic: every input byte read once (plus one 24-byte neighbour read per
 // lane and tile), every output byte written once.
-#include "bq_device.h"
+#include "bq_rowtile.h"
 #include "binquant_amd.h"
 
 #include <stddef.h>
@@ -214,8 +214,6 @@ __device__ __forceinline__ double ema_step(double y, double x, const EmaConsts& 
   }
 }
 
-typedef double dbl2 __attribute__((ext_vector_type(2)));
-
 // c ? a : b on the two halves. A select whose operand is a one-use fp64
 // operation is turned back into a branch late in code generation (the operand
 // and the LDS reads feeding it sink into the branch); selects of the halves
@@ -224,21 +222,6 @@ __device__ __forceinline__ double sel_f64(bool c, double a, double b) {
   const int hi = c ? __double2hiint(a) : __double2hiint(b);
   const int lo = c ? __double2loint(a) : __double2loint(b);
   return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ void load4(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[EN_K]) {
-  if (vec && tb + EN_K <= T) {
-    const dbl2* p = reinterpret_cast<const dbl2*>(row + tb);
-#pragma unroll
-    for (int j = 0; j < EN_K / 2; ++j) {
-      const dbl2 a = p[j];
-      x[2 * j] = a.x;
-      x[2 * j + 1] = a.y;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < EN_K; ++k) x[k] = (tb + k < T) ? row[tb + k] : 0.0;
-  }
 }
 
 // Output pointers are re-read from LDS each tile (see sA), which leaves the
@@ -338,11 +321,11 @@ __device__ __forceinline__ void load_tile(const EnrichArgs& A, int64_t row, int 
     load_pieces<EN_K>(A.in[BQ_CLOSE] + row, tb, T, t.c, 0.0);
     load_pieces<EN_K>(A.in[BQ_VOLUME] + row, tb, T, t.v, 0.0);
   } else {
-    load4(A.in[BQ_OPEN] + row, tb, T, vin, t.o);
-    load4(A.in[BQ_HIGH] + row, tb, T, vin, t.h);
-    load4(A.in[BQ_LOW] + row, tb, T, vin, t.l);
-    load4(A.in[BQ_CLOSE] + row, tb, T, vin, t.c);
-    load4(A.in[BQ_VOLUME] + row, tb, T, vin, t.v);
+    load_lane<EN_K, false>(A.in[BQ_OPEN] + row, tb, T, vin, t.o);
+    load_lane<EN_K, false>(A.in[BQ_HIGH] + row, tb, T, vin, t.h);
+    load_lane<EN_K, false>(A.in[BQ_LOW] + row, tb, T, vin, t.l);
+    load_lane<EN_K, false>(A.in[BQ_CLOSE] + row, tb, T, vin, t.c);
+    load_lane<EN_K, false>(A.in[BQ_VOLUME] + row, tb, T, vin, t.v);
   }
   if (tb >= 1 && tb <= T) {
     t.ph = A.in[BQ_HIGH][row + tb - 1];
@@ -1272,12 +1255,7 @@ int bq_enrich(const double* const* in, int64_t S, int64_t T, int64_t ld_in, cons
   A.ema = ema_consts(A.span);
 
   // 16-byte vector access needs every row start 16-byte aligned.
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  int vin = (ld_in % 2) == 0;
-  for (int i = 0; i < BQ_NUM_INPUTS; ++i) vin &= aligned(in[i]);
-  int vout = (ld_out % 2) == 0;
-  for (int i = 0; i < BQ_NUM_ENRICH_COLS; ++i)
-    if (out[i]) vout &= aligned(out[i]);
+  const int vin = vec_rows(in, BQ_NUM_INPUTS, ld_in), vout = vec_rows(out, BQ_NUM_ENRICH_COLS, ld_out);
 
   // does any EMA need the explicit `/ (old_wt + new_wt)` (non-unit sum)?
   bool div = false;

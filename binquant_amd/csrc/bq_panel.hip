@@ -33,60 +33,23 @@
 // bq_roll_job.panel == 0 (the live path and every bit-exact test).
 #include "bq_panel.h"
 
-#include "bq_device.h"
+#include "bq_rowtile.h"
 #include "binquant_amd.h"
 
 #include <string.h>
 
 namespace bq {
 
-constexpr int PN_NT = 256;
-constexpr int PN_NW = PN_NT / WAVE;
-constexpr int PN_K = 8;
-constexpr int PN_TT = PN_NT * PN_K;   // 2048
-constexpr int PN_H = 128;             // >= window + shift
-constexpr int PN_R = PN_H + PN_TT;    // 2176
-constexpr int PN_Q = PN_R / PN_K;     // 272
-
-__device__ __forceinline__ int pn_slot(int p) { return (p & (PN_K - 1)) * PN_Q + (p >> 3); }
-
-typedef double pn_dbl2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void pn_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[PN_K]) {
-  if (vec && tb + PN_K <= T) {
-    const pn_dbl2* p = reinterpret_cast<const pn_dbl2*>(row + tb);
-#pragma unroll
-    for (int j = 0; j < PN_K / 2; ++j) {
-      const pn_dbl2 a = p[j];
-      x[2 * j] = a.x;
-      x[2 * j + 1] = a.y;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < PN_K; ++k) x[k] = tb + k < T ? row[tb + k] : qnan();
-  }
-}
-
-__device__ __forceinline__ bool pn_aligned(const void* p, int64_t ld) { return (((uintptr_t)p) & 15u) == 0 && (ld % 2) == 0; }
-
-// exclusive block max of a per-lane int >= -1 combined with the tile carry
-// `*carry` — read after the barrier: the previous tile's last thread writes it
-// after that tile's final barrier, so a read before this one would race
-__device__ __forceinline__ int pn_block_excl_max(int v, const int* carry, int* sW, int lane, int w) {
-  const int inc = wave_scan_max_dpp(v + 1, lane) - 1;
-  if (lane == WAVE - 1) sW[w] = inc;
-  const int lpre = dpp_i32<DPP_WAVE_SHR1>(inc + 1) - 1;
-  __syncthreads();
-  int c = max(*carry, lpre);
-  for (int u = 0; u < w; ++u) c = max(c, sW[u]);
-  return c;
-}
+// 256 threads, 8 candles per lane (tiles of 2048, ring of 2176 in 8 planes of
+// 272); halo 128 >= window + shift. The jobs of a batch each bring their own
+// arrays, so the vector-path test (vec_row) runs in the kernel.
+using PN = RowTile<256, 8, 128>;
 
 // ---- sum / mean -----------------------------------------------------------------------
-__global__ __launch_bounds__(PN_NT) void panel_window_kernel(const PanelBatch B) {
-  __shared__ double sX[PN_R];
-  __shared__ int sL[PN_R];   // run start (last index where the value changed) per ring position
-  __shared__ int sW[PN_NW];
+__global__ __launch_bounds__(PN::NT) void panel_window_kernel(const PanelBatch B) {
+  __shared__ double sX[PN::R];
+  __shared__ int sL[PN::R];   // run start (last index where the value changed) per ring position
+  __shared__ int sW[PN::NW];
   __shared__ int sCar;
   const PanelJob& A = B.j[blockIdx.y];
   const int64_t row = blockIdx.x;
@@ -96,40 +59,40 @@ __global__ __launch_bounds__(PN_NT) void panel_window_kernel(const PanelBatch B)
   double* __restrict__ out = A.out + row * A.ld_out;
   const int T = B.T, win = A.win, sh = A.shift, minp = A.minp;
   const bool mean = A.mode == BQ_ROLL_MEAN;
-  const bool vin = pn_aligned(A.x, A.ld_in), vout = pn_aligned(A.out, A.ld_out);
-  if (tid < PN_H) {   // before the row: missing values
-    sX[pn_slot(tid)] = qnan();
-    sL[pn_slot(tid)] = -1;
+  const bool vin = vec_row(A.x, A.ld_in), vout = vec_row(A.out, A.ld_out);
+  if (tid < PN::H) {   // before the row: missing values
+    sX[PN::slot(tid)] = qnan();
+    sL[PN::slot(tid)] = -1;
   }
   if (tid == 0) sCar = -1;
-  double nx[PN_K];
-  pn_load(x, PN_K * tid, T, vin, nx);
-  for (int t0 = 0; t0 < T; t0 += PN_TT) {
-    const int tb = t0 + PN_K * tid, pb = PN_H + PN_K * tid;
-    double c[PN_K];
+  double nx[PN::K];
+  load_lane<PN::K>(x, PN::K * tid, T, vin, nx);
+  for (int t0 = 0; t0 < T; t0 += PN::TT) {
+    const int tb = t0 + PN::K * tid, pb = PN::H + PN::K * tid;
+    double c[PN::K];
 #pragma unroll
-    for (int k = 0; k < PN_K; ++k) c[k] = win_val(nx[k]);   // +-inf is missing (pandas' window ops)
+    for (int k = 0; k < PN::K; ++k) c[k] = win_val(nx[k]);   // +-inf is missing (pandas' window ops)
     const double pc0 = tb >= 1 && tb <= T ? win_val(x[tb - 1]) : qnan();
-    if (t0 + PN_TT < T) pn_load(x, tb + PN_TT, T, vin, nx);
+    if (t0 + PN::TT < T) load_lane<PN::K>(x, tb + PN::TT, T, vin, nx);
     // run starts of the values (NaN counts as a change)
-    int lcl[PN_K];
+    int lcl[PN::K];
     {
       double pv = pc0;
       int run = -1;
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) {
+      for (int k = 0; k < PN::K; ++k) {
         if (tb + k == 0 || !(c[k] == pv)) run = tb + k;
         lcl[k] = run;
         pv = c[k];
       }
-      const int carry = pn_block_excl_max(lcl[PN_K - 1], &sCar, sW, lane, w);
+      const int carry = block_excl_max(lcl[PN::K - 1], &sCar, sW, lane, w);
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) lcl[k] = max(lcl[k], carry);
+      for (int k = 0; k < PN::K; ++k) lcl[k] = max(lcl[k], carry);
     }
 #pragma unroll
-    for (int k = 0; k < PN_K; ++k) {
-      sX[pn_slot(pb + k)] = c[k];
-      sL[pn_slot(pb + k)] = lcl[k];
+    for (int k = 0; k < PN::K; ++k) {
+      sX[PN::slot(pb + k)] = c[k];
+      sL[PN::slot(pb + k)] = lcl[k];
     }
     __syncthreads();
     // window of output t = tb + k: ring positions [pb + k - sh - win + 1, pb + k - sh]
@@ -137,18 +100,18 @@ __global__ __launch_bounds__(PN_NT) void panel_window_kernel(const PanelBatch B)
     int nobs = 0, neg = 0;
     const int e0 = pb - sh;   // position of the entering value of output k = 0
     for (int j = 1 - win; j <= 0; ++j) {
-      const double v = sX[pn_slot(e0 + j)];
+      const double v = sX[PN::slot(e0 + j)];
       const bool ok = v == v;
       s += ok ? v : 0.0;
       nobs += ok;
       neg += ok && signbit(v);
     }
-    double res[PN_K];
+    double res[PN::K];
 #pragma unroll
-    for (int k = 0; k < PN_K; ++k) {
+    for (int k = 0; k < PN::K; ++k) {
       const int e = e0 + k;   // entering position
       if (k > 0) {
-        const double vi = sX[pn_slot(e)], vo = sX[pn_slot(e - win)];
+        const double vi = sX[PN::slot(e)], vo = sX[PN::slot(e - win)];
         const bool oi = vi == vi, oo = vo == vo;
         s = (s + (oi ? vi : 0.0)) - (oo ? vo : 0.0);
         nobs += (int)oi - (int)oo;
@@ -162,13 +125,13 @@ __global__ __launch_bounds__(PN_NT) void panel_window_kernel(const PanelBatch B)
         bool same;
         double last;
         if (nobs == win) {   // no missing value: the run start decides
-          last = sX[pn_slot(e)];
-          same = sL[pn_slot(e)] <= tb + k - sh - win + 1;
+          last = sX[PN::slot(e)];
+          same = sL[PN::slot(e)] <= tb + k - sh - win + 1;
         } else {             // missing values: compare the observed ones directly
           last = qnan();
           same = true;
           for (int j = 0; j > -win; --j) {
-            const double v = sX[pn_slot(e + j)];
+            const double v = sX[PN::slot(e + j)];
             if (v != v) continue;
             if (last != last) last = v;
             else same = same && v == last;
@@ -185,17 +148,17 @@ __global__ __launch_bounds__(PN_NT) void panel_window_kernel(const PanelBatch B)
       }
       res[k] = r;
     }
-    store_lines<PN_K>(out, tb, T, vout, res);
-    if (t0 + PN_TT >= T) break;
+    store_lines<PN::K>(out, tb, T, vout, res);
+    if (t0 + PN::TT >= T) break;
     __syncthreads();   // every read of this tile's ring is done
-    if (pb >= PN_TT) {
+    if (pb >= PN::TT) {
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) {
-        sX[pn_slot(pb + k - PN_TT)] = c[k];
-        sL[pn_slot(pb + k - PN_TT)] = lcl[k];
+      for (int k = 0; k < PN::K; ++k) {
+        sX[PN::slot(pb + k - PN::TT)] = c[k];
+        sL[PN::slot(pb + k - PN::TT)] = lcl[k];
       }
     }
-    if (tid == PN_NT - 1) sCar = lcl[PN_K - 1];
+    if (tid == PN::NT - 1) sCar = lcl[PN::K - 1];
   }
 }
 
@@ -205,10 +168,10 @@ __global__ __launch_bounds__(PN_NT) void panel_window_kernel(const PanelBatch B)
 // as DataFrame.max(axis=1): the first candle's is h - l) — the ATR of
 // liquidation_sweep_pump.py:206-217 without a true-range column in HBM
 template <bool TR>
-__global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
-  __shared__ double sA[PN_NW], sB[PN_NW];
+__global__ __launch_bounds__(PN::NT) void panel_ewm_kernel(const PanelBatch B) {
+  __shared__ double sA[PN::NW], sB[PN::NW];
   __shared__ double sCarry;
-  __shared__ double sX[PN_TT];   // the serial replay's tile
+  __shared__ double sX[PN::TT];   // the serial replay's tile
   const PanelJob& A = B.j[blockIdx.y];
   const int64_t row = blockIdx.x;
   if (row >= A.rows) return;
@@ -216,7 +179,7 @@ __global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
   const double* __restrict__ x = A.x + row * A.ld_in;
   double* __restrict__ out = A.out + row * A.ld_out;
   const int T = B.T, minp = A.minp;
-  const bool vin = pn_aligned(A.x, A.ld_in), vout = pn_aligned(A.out, A.ld_out);
+  const bool vin = vec_row(A.x, A.ld_in), vout = vec_row(A.out, A.ld_out);
   const double alpha = A.alpha, om = 1.0 - alpha, den = om + alpha;
   const bool div = den != 1.0;
   const double la = om / den, lb = alpha / den;
@@ -224,37 +187,37 @@ __global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
   bool serial = false;
   double wv = qnan(), owt = 1.0;   // pandas' state (thread 0) once the row turns serial
   int nobs = 0;
-  double nx[PN_K], nh[TR ? PN_K : 1], nl[TR ? PN_K : 1];
+  double nx[PN::K], nh[TR ? PN::K : 1], nl[TR ? PN::K : 1];
   const double* __restrict__ xh = TR ? A.hi + row * A.ld_in : nullptr;
   const double* __restrict__ xl = TR ? A.lo + row * A.ld_in : nullptr;
-  const bool vhl = TR && pn_aligned(A.hi, A.ld_in) && pn_aligned(A.lo, A.ld_in);
+  const bool vhl = TR && vec_row(A.hi, A.ld_in) && vec_row(A.lo, A.ld_in);
   auto load_tile = [&](int tb) {
-    pn_load(x, tb, T, vin, nx);
+    load_lane<PN::K>(x, tb, T, vin, nx);
     if constexpr (TR) {
-      pn_load(xh, tb, T, vhl, nh);
-      pn_load(xl, tb, T, vhl, nl);
+      load_lane<PN::K>(xh, tb, T, vhl, nh);
+      load_lane<PN::K>(xl, tb, T, vhl, nl);
     }
   };
-  load_tile(PN_K * tid);
-  for (int t0 = 0; t0 < T; t0 += PN_TT) {
-    const int tb = t0 + PN_K * tid;
-    double c[PN_K];
+  load_tile(PN::K * tid);
+  for (int t0 = 0; t0 < T; t0 += PN::TT) {
+    const int tb = t0 + PN::K * tid;
+    double c[PN::K];
     if constexpr (TR) {
       double pc = tb >= 1 && tb <= T ? x[tb - 1] : qnan();
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) {
+      for (int k = 0; k < PN::K; ++k) {
         c[k] = tb + k < T ? win_val(true_range(nh[k], nl[k], pc)) : qnan();
         pc = nx[k];
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) c[k] = win_val(nx[k]);   // +-inf is missing (pandas' window ops)
+      for (int k = 0; k < PN::K; ++k) c[k] = win_val(nx[k]);   // +-inf is missing (pandas' window ops)
     }
-    if (t0 + PN_TT < T) load_tile(tb + PN_TT);
+    if (t0 + PN::TT < T) load_tile(tb + PN::TT);
     {
       int bad = 0;
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) bad |= (tb + k < T) && !(c[k] - c[k] == 0.0);
+      for (int k = 0; k < PN::K; ++k) bad |= (tb + k < T) && !(c[k] - c[k] == 0.0);
       if (__syncthreads_or(bad) && !serial) {
         serial = true;
         if (t0 > 0) {   // candles 0 .. t0 - 1 were all observations
@@ -263,13 +226,13 @@ __global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
         }
       }
     }
-    double res[PN_K];
+    double res[PN::K];
     if (serial) {
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) sX[PN_K * tid + k] = c[k];
+      for (int k = 0; k < PN::K; ++k) sX[PN::K * tid + k] = c[k];
       __syncthreads();
       if (tid == 0) {
-        const int n = min(PN_TT, T - t0);
+        const int n = min(PN::TT, T - t0);
         for (int i = 0; i < n; ++i) {
           const double cur = sX[i];
           const bool obs = cur == cur;
@@ -296,16 +259,16 @@ __global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
       }
       __syncthreads();
 #pragma unroll
-      for (int k = 0; k < PN_K; ++k) res[k] = sX[PN_K * tid + k];
-      store_lines<PN_K>(out, tb, T, vout, res);
-      if (t0 + PN_TT >= T) break;
+      for (int k = 0; k < PN::K; ++k) res[k] = sX[PN::K * tid + k];
+      store_lines<PN::K>(out, tb, T, vout, res);
+      if (t0 + PN::TT >= T) break;
       __syncthreads();
       continue;
     }
     // lane map over its candles from the zero state (candle 0 resets: a = 0, b = x)
     double a_ = 1.0, b_ = 0.0;
 #pragma unroll
-    for (int k = 0; k < PN_K; ++k) {
+    for (int k = 0; k < PN::K; ++k) {
       if (tb + k == 0) {
         a_ = 0.0;
         b_ = c[k];
@@ -338,7 +301,7 @@ __global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
     y = fma(ea, y, eb);
     // exact replay of the lane's steps
 #pragma unroll
-    for (int k = 0; k < PN_K; ++k) {
+    for (int k = 0; k < PN::K; ++k) {
       const int t = tb + k;
       const double v = c[k];
       if (t == 0) y = v;
@@ -348,17 +311,17 @@ __global__ __launch_bounds__(PN_NT) void panel_ewm_kernel(const PanelBatch B) {
       }
       res[k] = t + 1 >= minp ? y : qnan();
     }
-    store_lines<PN_K>(out, tb, T, vout, res);
-    if (t0 + PN_TT >= T) break;
+    store_lines<PN::K>(out, tb, T, vout, res);
+    if (t0 + PN::TT >= T) break;
     __syncthreads();
-    if (tid == PN_NT - 1) sCarry = y;
+    if (tid == PN::NT - 1) sCarry = y;
     __syncthreads();
   }
 }
 
 bool panel_supported(int mode, int window, int shift) {
   if (mode == BQ_ROLL_EWM) return true;
-  return (mode == BQ_ROLL_SUM || mode == BQ_ROLL_MEAN) && window >= 1 && shift >= 0 && window + shift <= PN_H;
+  return (mode == BQ_ROLL_SUM || mode == BQ_ROLL_MEAN) && window >= 1 && shift >= 0 && window + shift <= PN::H;
 }
 
 void launch_panel(const PanelBatch& B, int n, hipStream_t st) {
@@ -374,9 +337,9 @@ void launch_panel(const PanelBatch& B, int n, hipStream_t st) {
     else if (B.j[i].mode == BQ_ROLL_EWM) ewm.j[ne++] = B.j[i];
     else win.j[nw++] = B.j[i];
   }
-  if (nw) hipLaunchKernelGGL(panel_window_kernel, dim3((unsigned)B.S, (unsigned)nw), dim3(PN_NT), 0, st, win);
-  if (ne) hipLaunchKernelGGL(panel_ewm_kernel<false>, dim3((unsigned)B.S, (unsigned)ne), dim3(PN_NT), 0, st, ewm);
-  if (nt) hipLaunchKernelGGL(panel_ewm_kernel<true>, dim3((unsigned)B.S, (unsigned)nt), dim3(PN_NT), 0, st, etr);
+  if (nw) hipLaunchKernelGGL(panel_window_kernel, dim3((unsigned)B.S, (unsigned)nw), dim3(PN::NT), 0, st, win);
+  if (ne) hipLaunchKernelGGL(panel_ewm_kernel<false>, dim3((unsigned)B.S, (unsigned)ne), dim3(PN::NT), 0, st, ewm);
+  if (nt) hipLaunchKernelGGL(panel_ewm_kernel<true>, dim3((unsigned)B.S, (unsigned)nt), dim3(PN::NT), 0, st, etr);
 }
 
 // LiquidationSweepPump's three ewm columns in ONE pass per row
@@ -414,21 +377,6 @@ constexpr int P3_NT = 2048 / P3_K;
 constexpr int P3_NW = P3_NT / WAVE;
 constexpr int P3_TT = P3_NT * P3_K;
 
-__device__ __forceinline__ void p3_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[P3_K]) {
-  if (vec && tb + P3_K <= T) {
-    const pn_dbl2* p = reinterpret_cast<const pn_dbl2*>(row + tb);
-#pragma unroll
-    for (int j = 0; j < P3_K / 2; ++j) {
-      const pn_dbl2 a = p[j];
-      x[2 * j] = a.x;
-      x[2 * j + 1] = a.y;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < P3_K; ++k) x[k] = tb + k < T ? row[tb + k] : qnan();
-  }
-}
-
 __global__ __launch_bounds__(P3_NT, BQ_P3_WPS) void pump_ewm3_kernel(const PumpEwmArgs A) {
   __shared__ double sA[P3_NW], sB[P3_NW];
   __shared__ double sCarry[3];
@@ -457,9 +405,9 @@ __global__ __launch_bounds__(P3_NT, BQ_P3_WPS) void pump_ewm3_kernel(const PumpE
     double v[2][P3_K];   // the true range; the close (+-inf: missing)
     {
       double nh[P3_K], nl[P3_K], nc[P3_K];
-      p3_load(xh, tb, T, vin, nh);
-      p3_load(xl, tb, T, vin, nl);
-      p3_load(xc, tb, T, vin, nc);
+      load_lane<P3_K>(xh, tb, T, vin, nh);
+      load_lane<P3_K>(xl, tb, T, vin, nl);
+      load_lane<P3_K>(xc, tb, T, vin, nc);
       double pc = tb >= 1 && tb <= T ? xc[tb - 1] : qnan();
 #pragma unroll
       for (int k = 0; k < P3_K; ++k) {
@@ -623,10 +571,10 @@ extern "C" int bq_pump_ewm(const double* high, const double* low, const double* 
   A.ld_in = ld_in;
   A.ld_out = ld_out;
   A.T = (int)T;
-  auto aligned = [](const void* p, int64_t ld) { return (((uintptr_t)p) & 15u) == 0 && (ld % 2) == 0; };
-  A.vin = aligned(high, ld_in) && aligned(low, ld_in) && aligned(close, ld_in);
-  A.vout = aligned(atr, ld_out) && aligned(ema20, ld_out) && aligned(ema50, ld_out) &&
-           (!trend_score || aligned(trend_score, ld_out));
+  const double* const hlc[3] = {high, low, close};
+  const double* const cols[4] = {atr, ema20, ema50, trend_score};
+  A.vin = vec_rows(hlc, 3, ld_in);
+  A.vout = vec_rows(cols, 4, ld_out);
   // pandas: alpha = 1 / (1 + com), com = 1 / alpha - 1 or (span - 1) / 2
   const double coms[3] = {1.0 / (1.0 / 14.0) - 1.0, (20.0 - 1.0) / 2.0, (50.0 - 1.0) / 2.0};
   const int minp[3] = {14, 0, 0};

@@ -26,7 +26,7 @@
 // intermediate (TR aside: the volume mean, the highs / lows window, the
 // ffilled close, momentum_3, pump_score ...): ~2.4x its algorithmic bytes.
 //
-// Mapping (as bq_enrich): one 256-thread workgroup per symbol walks its row in
+// Mapping (bq_rowtile.h): one 256-thread workgroup per symbol walks its row in
 // tiles of 1024 candles (4 per lane, 3 workgroups per CU); an LDS
 // ring with a 32-candle halo holds high, low, close, volume, the ffilled
 // close and the volume's run starts (the same-value rule), so every window
@@ -35,7 +35,7 @@
 // reference's operation order (the JIT stages' IEEE operations), so those
 // columns equal the staged pipeline given the same window values; the volume
 // mean's sliding sum agrees with pandas' Kahan roll_mean to rounding.
-#include "bq_device.h"
+#include "bq_rowtile.h"
 #include "binquant_amd.h"
 
 #include <stdint.h>
@@ -43,16 +43,10 @@
 
 namespace bq {
 
-constexpr int PF_NT = 256;
-constexpr int PF_NW = PF_NT / WAVE;
-constexpr int PF_K = 4;
-constexpr int PF_TT = PF_NT * PF_K;   // 1024
-constexpr int PF_H = 32;              // halo >= the longest lookback (volume window + shift)
-constexpr int PF_R = PF_H + PF_TT;
-constexpr int PF_Q = PF_R / PF_K;
-constexpr int PF_MAXW = PF_H - 1;
-// lane-interleaved ring (conflict-free: the lanes' k-th candles side by side)
-__device__ __forceinline__ int pf_slot(int p) { return (p & (PF_K - 1)) * PF_Q + (p >> 2); }
+// 256 threads, 4 candles per lane (tiles of 1024); halo 32 >= the longest
+// lookback (volume window + shift)
+using PF = RowTile<256, 4, 32>;
+constexpr int PF_MAXW = PF::H - 1;
 
 enum { PF_H_IN = 0, PF_L_IN, PF_C_IN, PF_V_IN, PF_ATR_IN, PF_E20_IN, PF_E50_IN, PF_NIN };
 
@@ -74,22 +68,6 @@ struct PumpArgs {
   PumpEwm ew[3];                       // EWM_IN: TR (atr), close span 20, close span 50
 };
 
-typedef double pf_dbl2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void pf_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[PF_K]) {
-  if (vec && tb + PF_K <= T) {
-    const pf_dbl2* p = reinterpret_cast<const pf_dbl2*>(row + tb);
-    const pf_dbl2 a = p[0], b = p[1];
-    x[0] = a.x;
-    x[1] = a.y;
-    x[2] = b.x;
-    x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < PF_K; ++k) x[k] = tb + k < T ? row[tb + k] : qnan();
-  }
-}
-
 // Series.clip(lower=0) / .replace(0, nan) as the staged programs evaluate them
 __device__ __forceinline__ double clip0(double x) { return x < 0.0 ? 0.0 : x; }
 __device__ __forceinline__ double rep0(double x) { return x == 0.0 ? qnan() : x; }
@@ -101,22 +79,22 @@ __device__ __forceinline__ double rep0(double x) { return x == 0.0 ? qnan() : x;
 // window as compile-time constants (PumpParams' defaults 3 / 20 / 6): the
 // window walks unroll, their ring slots become immediate offsets
 template <bool EWM_IN, int MC = 0, int VWC = 0, int CWC = 0>
-__global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(const PumpArgs A, int vin, int vout) {
-  __shared__ double sH[PF_R], sL[PF_R], sC[PF_R], sV[PF_R], sF[PF_R];
-  __shared__ double sEB[EWM_IN ? 3 : 1][PF_NW];   // the waves' scan totals
+__global__ __launch_bounds__(PF::NT, EWM_IN ? 2 : 3) void pump_features_kernel(const PumpArgs A, int vin, int vout) {
+  __shared__ double sH[PF::R], sL[PF::R], sC[PF::R], sV[PF::R], sF[PF::R];
+  __shared__ double sEB[EWM_IN ? 3 : 1][PF::NW];   // the waves' scan totals
   __shared__ double sEC[EWM_IN ? 3 : 1];          // the ewm values at the previous tile's last candle
   __shared__ int sBad;                            // series (bits) with a non-finite value in this tile
-  __shared__ int sRV[PF_R];   // volume run start (last index where the value changed; NaN counts)
-  __shared__ int sWv[PF_NW], sWc[PF_NW];
+  __shared__ int sRV[PF::R];   // volume run start (last index where the value changed; NaN counts)
+  __shared__ int sWv[PF::NW], sWc[PF::NW];
   __shared__ int sCv, sCc;    // carries: volume run start, last valid close index
   __shared__ double sFV;      // ffilled close at the end of the previous tile
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
   const int64_t sym = blockIdx.x;
   const int T = A.T, M = MC > 0 ? MC : A.mom, VW = VWC > 0 ? VWC : A.vol_w, CW = CWC > 0 ? CWC : A.comp_w;
   const int64_t irow = sym * A.ld_in, orow = sym * A.ld_out;
-  if (tid < PF_H) {   // before the row: missing values
-    sH[pf_slot(tid)] = sL[pf_slot(tid)] = sC[pf_slot(tid)] = sV[pf_slot(tid)] = sF[pf_slot(tid)] = qnan();
-    sRV[pf_slot(tid)] = -1;
+  if (tid < PF::H) {   // before the row: missing values
+    sH[PF::slot(tid)] = sL[PF::slot(tid)] = sC[PF::slot(tid)] = sV[PF::slot(tid)] = sF[PF::slot(tid)] = qnan();
+    sRV[PF::slot(tid)] = -1;
   }
   if (tid == 0) {
     sCv = -1;
@@ -146,31 +124,31 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
   // their own tile (no prefetch: see the launch bounds)
   constexpr int NP = PF_V_IN + 1;
 
-  for (int t0 = 0; t0 < T; t0 += PF_TT) {
-    const int tb = t0 + PF_K * tid, pb = PF_H + PF_K * tid;
-    double x[NP][PF_K], atr[PF_K], e20[PF_K], e50[PF_K], ewy[3] = {0.0, 0.0, 0.0};
+  for (int t0 = 0; t0 < T; t0 += PF::TT) {
+    const int tb = t0 + PF::K * tid, pb = PF::H + PF::K * tid;
+    double x[NP][PF::K], atr[PF::K], e20[PF::K], e50[PF::K], ewy[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-    for (int f = 0; f < NP; ++f) pf_load(A.in[f] + irow, tb, T, vin, x[f]);
+    for (int f = 0; f < NP; ++f) load_lane<PF::K>(A.in[f] + irow, tb, T, vin, x[f]);
     if (!EWM_IN) {
-      pf_load(A.in[PF_ATR_IN] + irow, tb, T, vin, atr);
+      load_lane<PF::K>(A.in[PF_ATR_IN] + irow, tb, T, vin, atr);
       if (A.in[PF_E20_IN]) {   // NULL: trend_score came with the ewm columns (bq_pump_ewm)
-        pf_load(A.in[PF_E20_IN] + irow, tb, T, vin, e20);
-        pf_load(A.in[PF_E50_IN] + irow, tb, T, vin, e50);
+        load_lane<PF::K>(A.in[PF_E20_IN] + irow, tb, T, vin, e20);
+        load_lane<PF::K>(A.in[PF_E50_IN] + irow, tb, T, vin, e50);
       } else {
 #pragma unroll
-        for (int k = 0; k < PF_K; ++k) e20[k] = e50[k] = qnan();
+        for (int k = 0; k < PF::K; ++k) e20[k] = e50[k] = qnan();
       }
     }
     const double pv0 = tb >= 1 && tb <= T ? A.in[PF_V_IN][irow + tb - 1] : qnan();
     // ---- phase A: ring, run starts of the volume, last valid close (and the
     // ewm series' lane maps / wave scans)
-    int lrv[PF_K], lvc[PF_K];
-    double ewx[3], ewv[3][PF_K];
+    int lrv[PF::K], lvc[PF::K];
+    double ewx[3], ewv[3][PF::K];
     {
       double pv = pv0;
       int run = -1, val = -1;
 #pragma unroll
-      for (int k = 0; k < PF_K; ++k) {
+      for (int k = 0; k < PF::K; ++k) {
         const int t = tb + k;
         const double v = x[PF_V_IN][k];
         if (t == 0 || !(v == pv)) run = t;
@@ -179,13 +157,13 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         const double c = x[PF_C_IN][k];
         if (c == c && t < T) val = t;
         lvc[k] = val;
-        sH[pf_slot(pb + k)] = x[PF_H_IN][k];
-        sL[pf_slot(pb + k)] = x[PF_L_IN][k];
-        sC[pf_slot(pb + k)] = c;
-        sV[pf_slot(pb + k)] = v;
+        sH[PF::slot(pb + k)] = x[PF_H_IN][k];
+        sL[PF::slot(pb + k)] = x[PF_L_IN][k];
+        sC[PF::slot(pb + k)] = c;
+        sV[PF::slot(pb + k)] = v;
       }
-      const int iv = wave_scan_max_dpp(lrv[PF_K - 1] + 1, lane);   // +1: DPP's zero fill is the identity
-      const int ic = wave_scan_max_dpp(lvc[PF_K - 1] + 1, lane);
+      const int iv = wave_scan_max_dpp(lrv[PF::K - 1] + 1, lane);   // +1: DPP's zero fill is the identity
+      const int ic = wave_scan_max_dpp(lvc[PF::K - 1] + 1, lane);
       if (lane == WAVE - 1) {
         sWv[w] = iv - 1;
         sWc[w] = ic - 1;
@@ -195,11 +173,11 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
       if (EWM_IN) {
         // the series' values: the true range (previous close from the ring)
         // and the close; lane maps from the zero state (candle 0 resets)
-        double sv[3][PF_K];
+        double sv[3][PF::K];
         {
-          double pc = sC[pf_slot(pb - 1)];
+          double pc = sC[PF::slot(pb - 1)];
 #pragma unroll
-          for (int k = 0; k < PF_K; ++k) {
+          for (int k = 0; k < PF::K; ++k) {
             const double c = x[PF_C_IN][k];
             sv[0][k] = tb + k < T ? win_val(true_range(x[PF_H_IN][k], x[PF_L_IN][k], pc)) : qnan();
             sv[1][k] = sv[2][k] = win_val(c);   // ewm: +-inf is missing
@@ -211,7 +189,7 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         for (int e = 0; e < 3; ++e) {
           double y = 0.0;
 #pragma unroll
-          for (int k = 0; k < PF_K; ++k) {
+          for (int k = 0; k < PF::K; ++k) {
             const double v = sv[e][k];
             bad |= (tb + k < T && !(v - v == 0.0)) ? (1 << e) : 0;
             y = tb + k == 0 ? v : fma(A.ew[e].la, y, A.ew[e].lb * v);
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
           if (lane == WAVE - 1) sEB[e][w] = inc;
           ewx[e] = dpp_f64<DPP_WAVE_SHR1>(inc);   // exclusive (lane 0: the carry alone)
 #pragma unroll
-          for (int k = 0; k < PF_K; ++k) ewv[e][k] = sv[e][k];
+          for (int k = 0; k < PF::K; ++k) ewv[e][k] = sv[e][k];
         }
         if (bad) atomicOr(&sBad, bad);
       }
@@ -230,13 +208,13 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         cc = max(cc, sWc[u]);
       }
 #pragma unroll
-      for (int k = 0; k < PF_K; ++k) {
+      for (int k = 0; k < PF::K; ++k) {
         lrv[k] = max(lrv[k], cv);
         lvc[k] = max(lvc[k], cc);
-        sRV[pf_slot(pb + k)] = lrv[k];
+        sRV[PF::slot(pb + k)] = lrv[k];
         // ffill: the last valid close at or before t (in the ring, or carried)
         const int i = lvc[k];
-        sF[pf_slot(pb + k)] = i < 0 ? qnan() : (i >= t0 - PF_H ? sC[pf_slot(i - t0 + PF_H)] : sFV);
+        sF[PF::slot(pb + k)] = i < 0 ? qnan() : (i >= t0 - PF::H ? sC[PF::slot(i - t0 + PF::H)] : sFV);
       }
     }
     __syncthreads();   // B: ffilled close and run starts visible (and the ewm wave totals)
@@ -259,14 +237,14 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
           // pandas' recursion over the tile (thread 0, values from the ring),
           // results through the output column
           if (tid == 0) {
-            const int n = min(PF_TT, T - t0);
+            const int n = min(PF::TT, T - t0);
             double wv = swv[e], owt = sowt[e];
             int nobs = snobs[e];
             for (int i = 0; i < n; ++i) {
-              const int p = PF_H + i;
-              const double c = sC[pf_slot(p)];
+              const int p = PF::H + i;
+              const double c = sC[PF::slot(p)];
               const double cur = win_val(
-                  e == 0 ? true_range(sH[pf_slot(p)], sL[pf_slot(p)], t0 + i > 0 ? sC[pf_slot(p - 1)] : qnan()) : c);
+                  e == 0 ? true_range(sH[PF::slot(p)], sL[PF::slot(p)], t0 + i > 0 ? sC[PF::slot(p - 1)] : qnan()) : c);
               const bool obs = cur == cur;
               if (t0 + i == 0) {
                 wv = cur;
@@ -297,7 +275,7 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
           __threadfence();
           __syncthreads();
 #pragma unroll
-          for (int k = 0; k < PF_K; ++k)
+          for (int k = 0; k < PF::K; ++k)
             res[e][k] = tb + k < T ? __longlong_as_double((long long)__hip_atomic_load(
                                          reinterpret_cast<unsigned long long*>(eo[e] + orow + tb + k), __ATOMIC_RELAXED,
                                          __HIP_MEMORY_SCOPE_AGENT))
@@ -309,7 +287,7 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
           for (int u = 0; u < w; ++u) y = fma(P.mw, y, sEB[e][u]);
           y = lane == 0 ? y : fma(lpow[e], y, ewx[e]);
 #pragma unroll
-          for (int k = 0; k < PF_K; ++k) {   // pandas' update, step by step
+          for (int k = 0; k < PF::K; ++k) {   // pandas' update, step by step
             const int t = tb + k;
             const double v = ewv[e][k];
             if (t == 0) y = v;
@@ -325,28 +303,28 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
     }
 
     // ---- phase C: the lane's 4 candles; each column stored as soon as formed
-    const bool whole = t0 + PF_TT <= T, vo = vout != 0;
-    auto put = [&](int col, const double (&r)[PF_K]) {
-      if (A.out[col]) store_lines<PF_K>(A.out[col] + orow, tb, T, vo, r, whole);
+    const bool whole = t0 + PF::TT <= T, vo = vout != 0;
+    auto put = [&](int col, const double (&r)[PF::K]) {
+      if (A.out[col]) store_lines<PF::K>(A.out[col] + orow, tb, T, vo, r, whole);
     };
-    double m3[PF_K], rv[PF_K], comp[PF_K], hmax[PF_K], bm3[PF_K], r[PF_K];
+    double m3[PF::K], rv[PF::K], comp[PF::K], hmax[PF::K], bm3[PF::K], r[PF::K];
     {
       // volume.shift(1).rolling(VW).mean(): window = ring [p - VW, p - 1]
       double s = 0.0;
       int nobs = 0, neg = 0;
       for (int j = -VW; j <= -1; ++j) {
-        const double v = sV[pf_slot(pb + j)];
+        const double v = sV[PF::slot(pb + j)];
         const bool ok = win_ok(v);   // NaN and +-inf are missing (window op)
         s += ok ? v : 0.0;
         nobs += ok;
         neg += ok && signbit(v);
       }
-      double pc = sC[pf_slot(pb - 1)];
+      double pc = sC[PF::slot(pb - 1)];
 #pragma unroll
-      for (int k = 0; k < PF_K; ++k) {
+      for (int k = 0; k < PF::K; ++k) {
         const int t = tb + k, p = pb + k;
         if (k > 0) {
-          const double vi = sV[pf_slot(p - 1)], vo_ = sV[pf_slot(p - 1 - VW)];
+          const double vi = sV[PF::slot(p - 1)], vo_ = sV[PF::slot(p - 1 - VW)];
           const bool oi = win_ok(vi), oo = win_ok(vo_);
           s = (s + (oi ? vi : 0.0)) - (oo ? vo_ : 0.0);
           nobs += (int)oi - (int)oo;
@@ -355,8 +333,8 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         double vmean;
         if (nobs < VW || nobs <= 0) vmean = qnan();   // min_periods = window
         else {
-          const double last = sV[pf_slot(p - 1)];
-          const bool same = sRV[pf_slot(p - 1)] <= t - VW;   // every value equal to the last
+          const double last = sV[PF::slot(p - 1)];
+          const bool same = sRV[PF::slot(p - 1)] <= t - VW;   // every value equal to the last
           vmean = s / (double)nobs;
           if (same) vmean = last;
           else if (neg == 0 && vmean < 0.0) vmean = 0.0;
@@ -369,7 +347,7 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         double hm = -__builtin_inf(), lm = __builtin_inf();
         int nh = 0, nl = 0;
         for (int j = -CW; j <= -1; ++j) {
-          const double hv = sH[pf_slot(p + j)], lv = sL[pf_slot(p + j)];
+          const double hv = sH[PF::slot(p + j)], lv = sL[PF::slot(p + j)];
           nh += win_ok(hv);
           nl += win_ok(lv);
           hm = fmax(hm, hv);
@@ -379,7 +357,7 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         const double lmin = nl >= CW ? lm : qnan();
         const double prev = pc;   // close.shift(1)
         pc = x[PF_C_IN][k];
-        const double cf = sF[pf_slot(p)], cf3 = t >= M ? sF[pf_slot(p - M)] : qnan();
+        const double cf = sF[PF::slot(p)], cf3 = t >= M ? sF[PF::slot(p - M)] : qnan();
         m3[k] = cf / cf3 - 1.0;
         rv[k] = x[PF_V_IN][k] / vmean;
         comp[k] = (hmax[k] - lmin) / prev;
@@ -393,38 +371,38 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
     put(BQ_PUMP_RELATIVE_VOLUME, rv);
     put(BQ_PUMP_COMPRESSION, comp);
 #pragma unroll
-    for (int k = 0; k < PF_K; ++k) r[k] = rv[k] * clip0(m3[k]) / rep0(comp[k]);
+    for (int k = 0; k < PF::K; ++k) r[k] = rv[k] * clip0(m3[k]) / rep0(comp[k]);
     put(BQ_PUMP_SCORE, r);
     put(BQ_PUMP_PRIOR_HIGH, hmax);
 #pragma unroll
-    for (int k = 0; k < PF_K; ++k) r[k] = (x[PF_C_IN][k] - x[PF_L_IN][k]) / rep0(x[PF_H_IN][k] - x[PF_L_IN][k]);
+    for (int k = 0; k < PF::K; ++k) r[k] = (x[PF_C_IN][k] - x[PF_L_IN][k]) / rep0(x[PF_H_IN][k] - x[PF_L_IN][k]);
     put(BQ_PUMP_CLOSE_LOCATION, r);
     put(BQ_PUMP_EMA20, e20);
     put(BQ_PUMP_EMA50, e50);
 #pragma unroll
-    for (int k = 0; k < PF_K; ++k) r[k] = (e20[k] - e50[k]) / e50[k];
+    for (int k = 0; k < PF::K; ++k) r[k] = (e20[k] - e50[k]) / e50[k];
     put(BQ_PUMP_TREND_SCORE, r);
 #pragma unroll
-    for (int k = 0; k < PF_K; ++k) r[k] = m3[k] / (atr[k] / x[PF_C_IN][k]);
+    for (int k = 0; k < PF::K; ++k) r[k] = m3[k] / (atr[k] / x[PF_C_IN][k]);
     put(BQ_PUMP_MOMENTUM_ATR, r);
     put(BQ_PUMP_BTC_MOMENTUM_3, bm3);
 #pragma unroll
-    for (int k = 0; k < PF_K; ++k) {
+    for (int k = 0; k < PF::K; ++k) {
       const int t = tb + k;
       const double b20 = t < T ? A.be20[t] : qnan(), b50 = t < T ? A.be50[t] : qnan();
       r[k] = (b20 - b50) / b50;
     }
     put(BQ_PUMP_BTC_TREND_SCORE, r);
 #pragma unroll
-    for (int k = 0; k < PF_K; ++k) r[k] = m3[k] - bm3[k];
+    for (int k = 0; k < PF::K; ++k) r[k] = m3[k] - bm3[k];
     put(BQ_PUMP_RELATIVE_STRENGTH, r);
 
-    if (t0 + PF_TT >= T) break;
+    if (t0 + PF::TT >= T) break;
     __syncthreads();   // every read of this tile's ring is done
-    if (pb >= PF_TT) {   // halo of the next tile: the last PF_H positions
+    if (pb >= PF::TT) {   // halo of the next tile: the last PF::H positions
 #pragma unroll
-      for (int k = 0; k < PF_K; ++k) {
-        const int a = pf_slot(pb + k), d = pf_slot(pb + k - PF_TT);
+      for (int k = 0; k < PF::K; ++k) {
+        const int a = PF::slot(pb + k), d = PF::slot(pb + k - PF::TT);
         sH[d] = sH[a];
         sL[d] = sL[a];
         sC[d] = sC[a];
@@ -433,10 +411,10 @@ __global__ __launch_bounds__(PF_NT, EWM_IN ? 2 : 3) void pump_features_kernel(co
         sRV[d] = sRV[a];
       }
     }
-    if (tid == PF_NT - 1) {
-      sCv = lrv[PF_K - 1];
-      sCc = lvc[PF_K - 1];
-      sFV = sF[pf_slot(pb + PF_K - 1)];
+    if (tid == PF::NT - 1) {
+      sCv = lrv[PF::K - 1];
+      sCc = lvc[PF::K - 1];
+      sFV = sF[PF::slot(pb + PF::K - 1)];
       if (EWM_IN)
 #pragma unroll
         for (int e = 0; e < 3; ++e) sEC[e] = ewy[e];   // (serial series: unused)
@@ -452,11 +430,11 @@ extern "C" int bq_pump_features(const double* const* in, int64_t S, int64_t T, i
                                 int32_t momentum_bars, int32_t volume_lookback, int32_t compression_bars,
                                 double* const* out, int64_t ld_out, void* stream) {
   using namespace bq;
-  if (!in || !bench || !out || S < 0 || T < 0 || ld_in < T || ld_out < T || T > 0x7fffffff - 2 * PF_TT ||
+  if (!in || !bench || !out || S < 0 || T < 0 || ld_in < T || ld_out < T || T > 0x7fffffff - 2 * PF::TT ||
       S > 0x7fffffff)
     return BQ_EINVAL;
   if (momentum_bars < 1 || momentum_bars > PF_MAXW || volume_lookback < 1 || compression_bars < 1 ||
-      volume_lookback + 1 > PF_H || compression_bars + 1 > PF_H)
+      volume_lookback + 1 > PF::H || compression_bars + 1 > PF::H)
     return BQ_EINVAL;
   PumpArgs A;
   memset(&A, 0, sizeof(A));
@@ -485,17 +463,12 @@ extern "C" int bq_pump_features(const double* const* in, int64_t S, int64_t T, i
   A.mom = momentum_bars;
   A.vol_w = volume_lookback;
   A.comp_w = compression_bars;
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  int vin = (ld_in % 2) == 0, vout = (ld_out % 2) == 0;
-  for (int f = 0; f < PF_NIN; ++f)
-    if (in[f]) vin &= aligned(in[f]);
-  for (int c = 0; c < BQ_NUM_PUMP_COLS; ++c)
-    if (out[c]) vout &= aligned(out[c]);
+  const int vin = vec_rows(in, PF_NIN, ld_in), vout = vec_rows(out, BQ_NUM_PUMP_COLS, ld_out);
   if (momentum_bars == 3 && volume_lookback == 20 && compression_bars == 6)   // PumpParams' defaults
-    hipLaunchKernelGGL((pump_features_kernel<false, 3, 20, 6>), dim3((unsigned)S), dim3(PF_NT), 0, (hipStream_t)stream, A,
+    hipLaunchKernelGGL((pump_features_kernel<false, 3, 20, 6>), dim3((unsigned)S), dim3(PF::NT), 0, (hipStream_t)stream, A,
                        vin, vout);
   else
-    hipLaunchKernelGGL(pump_features_kernel<false>, dim3((unsigned)S), dim3(PF_NT), 0, (hipStream_t)stream, A, vin,
+    hipLaunchKernelGGL(pump_features_kernel<false>, dim3((unsigned)S), dim3(PF::NT), 0, (hipStream_t)stream, A, vin,
                        vout);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
@@ -522,11 +495,11 @@ extern "C" int bq_pump_features_ewm(const double* const* in, int64_t S, int64_t 
                                     const double* const* bench, int32_t momentum_bars, int32_t volume_lookback,
                                     int32_t compression_bars, double* const* out, int64_t ld_out, void* stream) {
   using namespace bq;
-  if (!in || !bench || !out || S < 0 || T < 0 || ld_in < T || ld_out < T || T > 0x7fffffff - 2 * PF_TT ||
+  if (!in || !bench || !out || S < 0 || T < 0 || ld_in < T || ld_out < T || T > 0x7fffffff - 2 * PF::TT ||
       S > 0x7fffffff)
     return BQ_EINVAL;
   if (momentum_bars < 1 || momentum_bars > PF_MAXW || volume_lookback < 1 || compression_bars < 1 ||
-      volume_lookback + 1 > PF_H || compression_bars + 1 > PF_H)
+      volume_lookback + 1 > PF::H || compression_bars + 1 > PF::H)
     return BQ_EINVAL;
   PumpArgs A;
   memset(&A, 0, sizeof(A));
@@ -553,11 +526,7 @@ extern "C" int bq_pump_features_ewm(const double* const* in, int64_t S, int64_t 
   pump_ewm_consts(A.ew[0], 1.0 / (1.0 / 14.0) - 1.0, 14);   // TR.ewm(alpha=1/14, min_periods=14) (:206-217)
   pump_ewm_consts(A.ew[1], (20.0 - 1.0) / 2.0, 0);          // close.ewm(span=20) (:252)
   pump_ewm_consts(A.ew[2], (50.0 - 1.0) / 2.0, 0);          // close.ewm(span=50) (:253)
-  auto aligned = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  int vin = (ld_in % 2) == 0, vout = (ld_out % 2) == 0;
-  for (int f = 0; f <= PF_V_IN; ++f) vin &= aligned(in[f]);
-  for (int c = 0; c < BQ_NUM_PUMP_COLS; ++c)
-    if (out[c]) vout &= aligned(out[c]);
-  hipLaunchKernelGGL(pump_features_kernel<true>, dim3((unsigned)S), dim3(PF_NT), 0, (hipStream_t)stream, A, vin, vout);
+  const int vin = vec_rows(in, PF_V_IN + 1, ld_in), vout = vec_rows(out, BQ_NUM_PUMP_COLS, ld_out);
+  hipLaunchKernelGGL(pump_features_kernel<true>, dim3((unsigned)S), dim3(PF::NT), 0, (hipStream_t)stream, A, vin, vout);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }

@@ -29,59 +29,16 @@
 // again once it has left); the Wilder RSI row is replayed serially with
 // pandas' ewm update from the first tile holding a non-finite close (gap
 // decay, observation count, a late first observation).
-#include "bq_device.h"
+#include "bq_rowtile.h"
 #include "binquant_amd.h"
 
 #include <string.h>
 
 namespace bq {
 
-constexpr int SG_NT = 256;
-constexpr int SG_NW = SG_NT / WAVE;
-constexpr int SG_K = 8;
-constexpr int SG_TT = SG_NT * SG_K;   // 2048
-constexpr int SG_H = 128;
-constexpr int SG_R = SG_H + SG_TT;    // 2176
-constexpr int SG_Q = SG_R / SG_K;     // 272
-static_assert(SG_R % SG_K == 0 && SG_H % SG_K == 0, "ring shape");
-
-// ring position p -> LDS slot (lane-interleaved)
-__device__ __forceinline__ int sg_slot(int p) { return (p & (SG_K - 1)) * SG_Q + (p >> 3); }
-
-typedef double sg_dbl2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void sg_load(const double* __restrict__ row, int tb, int T, bool vec, double (&x)[SG_K]) {
-  if (vec && tb + SG_K <= T) {
-    const sg_dbl2* p = reinterpret_cast<const sg_dbl2*>(row + tb);
-#pragma unroll
-    for (int j = 0; j < SG_K / 2; ++j) {
-      const sg_dbl2 a = p[j];
-      x[2 * j] = a.x;
-      x[2 * j + 1] = a.y;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < SG_K; ++k) x[k] = tb + k < T ? row[tb + k] : qnan();
-  }
-}
-
-// whole-line stores (bq_device.h store_lines); every thread of the block calls it
-__device__ __forceinline__ void sg_store(double* __restrict__ row, int tb, int T, bool vec, const double (&x)[SG_K]) {
-  store_lines<SG_K>(row, tb, T, vec, x);
-}
-
-// Block-wide inclusive max of a per-lane int (>= -1): wave DPP scan, wave
-// totals through LDS. Returns the exclusive prefix max over lower lanes
-// combined with `carry` (the value carried from previous tiles).
-__device__ __forceinline__ int sg_block_excl_max(int v, int carry, int* sW, int lane, int w) {
-  const int inc = wave_scan_max_dpp(v + 1, lane) - 1;
-  if (lane == WAVE - 1) sW[w] = inc;
-  const int lpre = dpp_i32<DPP_WAVE_SHR1>(inc + 1) - 1;   // lane 0 -> -1
-  __syncthreads();
-  int c = max(carry, lpre);
-  for (int u = 0; u < w; ++u) c = max(c, sW[u]);
-  return c;
-}
+// 256 threads, 8 candles per lane (tiles of 2048, ring of 2176 in 8 planes of
+// 272); halo 128 >= BQ_MAX_WINDOW, and twice the ADX window (bq_adx)
+using SG = RowTile<256, 8, 128>;
 
 struct SigArgs {
   const double* in[3];   // close | high, low, close
@@ -99,9 +56,9 @@ struct SigArgs {
 // W > 0: the window is the reference's (20), known at compile time, so the
 // window walks unroll completely (same operations, same order); W = 0: any.
 template <int W>
-__global__ __launch_bounds__(SG_NT) void zscore_kernel(const SigArgs A) {
-  __shared__ double sC[SG_R];
-  __shared__ int sW[SG_NW];
+__global__ __launch_bounds__(SG::NT) void zscore_kernel(const SigArgs A) {
+  __shared__ double sC[SG::R];
+  __shared__ int sW[SG::NW];
   __shared__ int sCar;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
   const int64_t sym = blockIdx.x;
@@ -109,51 +66,51 @@ __global__ __launch_bounds__(SG_NT) void zscore_kernel(const SigArgs A) {
   double* __restrict__ ro = A.out + sym * A.ld_out;
   const int T = A.T;
   const int win = W ? W : __builtin_amdgcn_readfirstlane(A.win);
-  if (tid < SG_H) sC[sg_slot(tid)] = qnan();
+  if (tid < SG::H) sC[SG::slot(tid)] = qnan();
   if (tid == 0) sCar = -1;
-  double nx[SG_K];
-  sg_load(rc, SG_K * tid, T, A.vin, nx);
-  for (int t0 = 0; t0 < T; t0 += SG_TT) {
-    const int tb = t0 + SG_K * tid, pb = SG_H + SG_K * tid;
-    double c[SG_K];
+  double nx[SG::K];
+  load_lane<SG::K>(rc, SG::K * tid, T, A.vin, nx);
+  for (int t0 = 0; t0 < T; t0 += SG::TT) {
+    const int tb = t0 + SG::K * tid, pb = SG::H + SG::K * tid;
+    double c[SG::K];
 #pragma unroll
-    for (int k = 0; k < SG_K; ++k) c[k] = nx[k];
-    if (t0 + SG_TT < T) sg_load(rc, tb + SG_TT, T, A.vin, nx);
+    for (int k = 0; k < SG::K; ++k) c[k] = nx[k];
+    if (t0 + SG::TT < T) load_lane<SG::K>(rc, tb + SG::TT, T, A.vin, nx);
 #pragma unroll
-    for (int k = 0; k < SG_K; ++k) sC[sg_slot(pb + k)] = c[k];
+    for (int k = 0; k < SG::K; ++k) sC[SG::slot(pb + k)] = c[k];
     __syncthreads();
     // last index where the close changed (pandas' same-value rule)
-    int lcl[SG_K];
+    int lcl[SG::K];
     {
-      double pc = sC[sg_slot(pb - 1)];
+      double pc = sC[SG::slot(pb - 1)];
       int run = -1;
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         if (tb + k == 0 || c[k] != pc) run = tb + k;
         lcl[k] = run;
         pc = c[k];
       }
-      const int carry = sg_block_excl_max(lcl[SG_K - 1], sCar, sW, lane, w);
+      const int carry = block_excl_max(lcl[SG::K - 1], &sCar, sW, lane, w);
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) lcl[k] = max(lcl[k], carry);
+      for (int k = 0; k < SG::K; ++k) lcl[k] = max(lcl[k], carry);
     }
-    double z[SG_K];
+    double z[SG::K];
     {
       // windows reaching before candle 0 (first tile only) hold only the
       // candles from 0 on; those outputs are warm-up, but the sliding sums
       // must not carry the halo's NaN into the first complete window
-      const int gs = SG_H - t0;   // ring position of candle 0
+      const int gs = SG::H - t0;   // ring position of candle 0
       // a finite lane-local reference (a missing candle is excluded from the
       // sums and counted: pandas' rolling(w, min_periods=w) is NaN while the
       // window holds one, z = 0 there, and finite again once it has left)
       double r = c[0];
 #pragma unroll
-      for (int k = 1; k < SG_K; ++k) r = r == r ? r : c[k];
+      for (int k = 1; k < SG::K; ++k) r = r == r ? r : c[k];
       r = r == r ? r : 0.0;
       double s1 = 0.0, s2 = 0.0;
       int nn = 0;
       auto walk = [&](int x0) {
-        const double v = sC[sg_slot(pb + x0)];
+        const double v = sC[SG::slot(pb + x0)];
         const bool ok = v == v;
         const double d = ok ? v - r : 0.0;
         nn += ok ? 0 : 1;
@@ -167,12 +124,12 @@ __global__ __launch_bounds__(SG_NT) void zscore_kernel(const SigArgs A) {
         for (int x = max(1 - win, gs - pb); x <= 0; ++x) walk(x);
       }
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         const int t = tb + k;
         if (k > 0) {
           const bool oi = c[k] == c[k];
           const double dn = oi ? c[k] - r : 0.0;
-          const double vo = pb + k - win >= gs ? sC[sg_slot(pb + k - win)] : r;
+          const double vo = pb + k - win >= gs ? sC[SG::slot(pb + k - win)] : r;
           const bool oo = vo == vo;
           const double dol = oo ? vo - r : 0.0;
           nn += (oi ? 0 : 1) - (oo ? 0 : 1);
@@ -189,14 +146,14 @@ __global__ __launch_bounds__(SG_NT) void zscore_kernel(const SigArgs A) {
         z[k] = v;
       }
     }
-    sg_store(ro, tb, T, A.vout, z);
-    if (t0 + SG_TT >= T) break;
+    store_lines<SG::K>(ro, tb, T, A.vout, z);
+    if (t0 + SG::TT >= T) break;
     __syncthreads();
-    if (pb >= SG_TT) {
+    if (pb >= SG::TT) {
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) sC[sg_slot(pb + k - SG_TT)] = c[k];
+      for (int k = 0; k < SG::K; ++k) sC[SG::slot(pb + k - SG::TT)] = c[k];
     }
-    if (tid == SG_NT - 1) sCar = lcl[SG_K - 1];
+    if (tid == SG::NT - 1) sCar = lcl[SG::K - 1];
   }
 }
 
@@ -205,9 +162,9 @@ __global__ __launch_bounds__(SG_NT) void zscore_kernel(const SigArgs A) {
 // DI = 100 * sum / atr_sum, dx = 100 |DI+ - DI-| / (DI+ + DI-) (0 for a zero
 // or NaN denominator, fillna(0)), adx = dx.rolling(w).mean(), 100 where NaN.
 template <int W>   // as zscore_kernel (the reference's window: 14)
-__global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
-  __shared__ double sTR[SG_R], sPD[SG_R], sMD[SG_R], sDX[SG_R];
-  __shared__ int sW[SG_NW], sW2[SG_NW];
+__global__ __launch_bounds__(SG::NT) void adx_kernel(const SigArgs A) {
+  __shared__ double sTR[SG::R], sPD[SG::R], sMD[SG::R], sDX[SG::R];
+  __shared__ int sW[SG::NW], sW2[SG::NW];
   __shared__ int sCar[2];
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
   const int64_t sym = blockIdx.x;
@@ -217,19 +174,19 @@ __global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
   double* __restrict__ ro = A.out + sym * A.ld_out;
   const int T = A.T;
   const int win = W ? W : __builtin_amdgcn_readfirstlane(A.win);
-  if (tid < SG_H) {
-    sTR[sg_slot(tid)] = sPD[sg_slot(tid)] = sMD[sg_slot(tid)] = sDX[sg_slot(tid)] = 0.0;
+  if (tid < SG::H) {
+    sTR[SG::slot(tid)] = sPD[SG::slot(tid)] = sMD[SG::slot(tid)] = sDX[SG::slot(tid)] = 0.0;
   }
   if (tid < 2) sCar[tid] = -1;
-  double nh[SG_K], nl[SG_K], nc[SG_K];
-  sg_load(rh, SG_K * tid, T, A.vin, nh);
-  sg_load(rl, SG_K * tid, T, A.vin, nl);
-  sg_load(rc, SG_K * tid, T, A.vin, nc);
-  for (int t0 = 0; t0 < T; t0 += SG_TT) {
-    const int tb = t0 + SG_K * tid, pb = SG_H + SG_K * tid;
-    double h[SG_K], l[SG_K], c[SG_K];
+  double nh[SG::K], nl[SG::K], nc[SG::K];
+  load_lane<SG::K>(rh, SG::K * tid, T, A.vin, nh);
+  load_lane<SG::K>(rl, SG::K * tid, T, A.vin, nl);
+  load_lane<SG::K>(rc, SG::K * tid, T, A.vin, nc);
+  for (int t0 = 0; t0 < T; t0 += SG::TT) {
+    const int tb = t0 + SG::K * tid, pb = SG::H + SG::K * tid;
+    double h[SG::K], l[SG::K], c[SG::K];
 #pragma unroll
-    for (int k = 0; k < SG_K; ++k) {
+    for (int k = 0; k < SG::K; ++k) {
       h[k] = nh[k];
       l[k] = nl[k];
       c[k] = nc[k];
@@ -237,23 +194,23 @@ __global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
     const double ph0 = tb >= 1 && tb <= T ? rh[tb - 1] : qnan();
     const double pl0 = tb >= 1 && tb <= T ? rl[tb - 1] : qnan();
     const double pc0 = tb >= 1 && tb <= T ? rc[tb - 1] : qnan();
-    if (t0 + SG_TT < T) {
-      sg_load(rh, tb + SG_TT, T, A.vin, nh);
-      sg_load(rl, tb + SG_TT, T, A.vin, nl);
-      sg_load(rc, tb + SG_TT, T, A.vin, nc);
+    if (t0 + SG::TT < T) {
+      load_lane<SG::K>(rh, tb + SG::TT, T, A.vin, nh);
+      load_lane<SG::K>(rl, tb + SG::TT, T, A.vin, nl);
+      load_lane<SG::K>(rc, tb + SG::TT, T, A.vin, nc);
     }
-    double tr[SG_K], pd[SG_K], md[SG_K];
+    double tr[SG::K], pd[SG::K], md[SG::K];
     {
       double ph = ph0, pl = pl0, pc = pc0;
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         tr[k] = true_range(h[k], l[k], pc);
         const double hd = h[k] - ph, ld = -(l[k] - pl);   // high.diff(), -low.diff()
         pd[k] = (hd > ld && hd > 0.0) ? hd : 0.0;
         md[k] = (ld > hd && ld > 0.0) ? ld : 0.0;
-        sTR[sg_slot(pb + k)] = tr[k];
-        sPD[sg_slot(pb + k)] = pd[k];
-        sMD[sg_slot(pb + k)] = md[k];
+        sTR[SG::slot(pb + k)] = tr[k];
+        sPD[SG::slot(pb + k)] = pd[k];
+        sMD[SG::slot(pb + k)] = md[k];
         ph = h[k];
         pl = l[k];
         pc = c[k];
@@ -261,24 +218,24 @@ __global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
     }
     __syncthreads();   // the ring (incl. the neighbour lanes' candles) is visible
     // constant-run starts of the three series (pandas' same-value rule for sums)
-    int ltr[SG_K];
+    int ltr[SG::K];
     {
-      double ptr = sTR[sg_slot(pb - 1)], ppd = sPD[sg_slot(pb - 1)], pmd = sMD[sg_slot(pb - 1)];
+      double ptr = sTR[SG::slot(pb - 1)], ppd = sPD[SG::slot(pb - 1)], pmd = sMD[SG::slot(pb - 1)];
       int run = -1;
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         if (tb + k == 0 || tr[k] != ptr || pd[k] != ppd || md[k] != pmd) run = tb + k;
         ltr[k] = run;
         ptr = tr[k];
         ppd = pd[k];
         pmd = md[k];
       }
-      const int carry = sg_block_excl_max(ltr[SG_K - 1], sCar[0], sW, lane, w);
+      const int carry = block_excl_max(ltr[SG::K - 1], &sCar[0], sW, lane, w);
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) ltr[k] = max(ltr[k], carry);
+      for (int k = 0; k < SG::K; ++k) ltr[k] = max(ltr[k], carry);
     }
     // dx of the lane's candles
-    double dx[SG_K];
+    double dx[SG::K];
     {
       // a true range that is NaN (a missing high / low / previous close the
       // skip-NaN max cannot cover) is excluded from the sliding sum and
@@ -287,17 +244,17 @@ __global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
       double st = 0.0, sp = 0.0, sm = 0.0;
       int nn = 0;
       walk_window<(W > 0)>(1 - win, [&](int x) {
-        const double a = sTR[sg_slot(pb + x)];
+        const double a = sTR[SG::slot(pb + x)];
         st += a == a ? a : 0.0;
         nn += a == a ? 0 : 1;
-        sp += sPD[sg_slot(pb + x)];
-        sm += sMD[sg_slot(pb + x)];
+        sp += sPD[SG::slot(pb + x)];
+        sm += sMD[SG::slot(pb + x)];
       });
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         const int t = tb + k;
         if (k > 0) {
-          const int o = sg_slot(pb + k - win);
+          const int o = SG::slot(pb + k - win);
           const double ai = tr[k], ao = sTR[o];
           st = (st + (ai == ai ? ai : 0.0)) - (ao == ao ? ao : 0.0);
           nn += (ai == ai ? 0 : 1) - (ao == ao ? 0 : 1);
@@ -318,32 +275,32 @@ __global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
           if (v != v) v = 0.0;
         }
         dx[k] = v;
-        sDX[sg_slot(pb + k)] = v;
+        sDX[SG::slot(pb + k)] = v;
       }
     }
     __syncthreads();   // dx of every lane visible
-    int ldx[SG_K];
+    int ldx[SG::K];
     {
-      double pv = sDX[sg_slot(pb - 1)];
+      double pv = sDX[SG::slot(pb - 1)];
       int run = -1;
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         if (tb + k == 0 || dx[k] != pv) run = tb + k;
         ldx[k] = run;
         pv = dx[k];
       }
-      const int carry = sg_block_excl_max(ldx[SG_K - 1], sCar[1], sW2, lane, w);
+      const int carry = block_excl_max(ldx[SG::K - 1], &sCar[1], sW2, lane, w);
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) ldx[k] = max(ldx[k], carry);
+      for (int k = 0; k < SG::K; ++k) ldx[k] = max(ldx[k], carry);
     }
-    double adx[SG_K];
+    double adx[SG::K];
     {
       double s = 0.0;
-      walk_window<(W > 0)>(1 - win, [&](int x) { s += sDX[sg_slot(pb + x)]; });
+      walk_window<(W > 0)>(1 - win, [&](int x) { s += sDX[SG::slot(pb + x)]; });
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         const int t = tb + k;
-        if (k > 0) s = (s + dx[k]) - sDX[sg_slot(pb + k - win)];
+        if (k > 0) s = (s + dx[k]) - sDX[SG::slot(pb + k - win)];
         double v = 100.0;
         if (t >= win - 1) {
           if (ldx[k] <= t - win + 1) v = dx[k];
@@ -352,22 +309,22 @@ __global__ __launch_bounds__(SG_NT) void adx_kernel(const SigArgs A) {
         adx[k] = v;
       }
     }
-    sg_store(ro, tb, T, A.vout, adx);
-    if (t0 + SG_TT >= T) break;
+    store_lines<SG::K>(ro, tb, T, A.vout, adx);
+    if (t0 + SG::TT >= T) break;
     __syncthreads();
-    if (pb >= SG_TT) {
+    if (pb >= SG::TT) {
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
-        const int d = sg_slot(pb + k - SG_TT);
+      for (int k = 0; k < SG::K; ++k) {
+        const int d = SG::slot(pb + k - SG::TT);
         sTR[d] = tr[k];
         sPD[d] = pd[k];
         sMD[d] = md[k];
         sDX[d] = dx[k];
       }
     }
-    if (tid == SG_NT - 1) {
-      sCar[0] = ltr[SG_K - 1];
-      sCar[1] = ldx[SG_K - 1];
+    if (tid == SG::NT - 1) {
+      sCar[0] = ltr[SG::K - 1];
+      sCar[1] = ldx[SG::K - 1];
     }
   }
 }
@@ -387,10 +344,10 @@ __device__ __forceinline__ double wilder_step(double y, double x, const SigArgs&
 }
 
 template <bool DIV>
-__global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
-  __shared__ double sA[SG_NW], sB[2][SG_NW];
+__global__ __launch_bounds__(SG::NT) void wilder_rsi_kernel(const SigArgs A) {
+  __shared__ double sA[SG::NW], sB[2][SG::NW];
   __shared__ double sCarry[2];
-  __shared__ double sX[SG_TT];   // the serial replay's tile (rows with missing candles)
+  __shared__ double sX[SG::TT];   // the serial replay's tile (rows with missing candles)
   __shared__ double sSt[4];      // its pandas state: avg gain, avg loss, old weight, previous close
   __shared__ int sNobs;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
@@ -409,15 +366,15 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
     sSt[2] = 1.0;
     sNobs = 0;
   }
-  double nx[SG_K];
-  sg_load(rc, SG_K * tid, T, A.vin, nx);
-  for (int t0 = 0; t0 < T; t0 += SG_TT) {
-    const int tb = t0 + SG_K * tid;
-    double c[SG_K];
+  double nx[SG::K];
+  load_lane<SG::K>(rc, SG::K * tid, T, A.vin, nx);
+  for (int t0 = 0; t0 < T; t0 += SG::TT) {
+    const int tb = t0 + SG::K * tid;
+    double c[SG::K];
 #pragma unroll
-    for (int k = 0; k < SG_K; ++k) c[k] = nx[k];
+    for (int k = 0; k < SG::K; ++k) c[k] = nx[k];
     const double pc0 = tb >= 1 && tb <= T ? rc[tb - 1] : qnan();
-    if (t0 + SG_TT < T) sg_load(rc, tb + SG_TT, T, A.vin, nx);
+    if (t0 + SG::TT < T) load_lane<SG::K>(rc, tb + SG::TT, T, A.vin, nx);
     // A missing (NaN) or infinite close breaks the scan's fixed per-candle
     // map: pandas' ewm(ignore_na=False) decays the old weight across a gap
     // and divides by (old_wt + alpha), counts only observations toward
@@ -428,7 +385,7 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
     {
       int bad = 0;
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) bad |= (tb + k < T) && !(c[k] - c[k] == 0.0);
+      for (int k = 0; k < SG::K; ++k) bad |= (tb + k < T) && !(c[k] - c[k] == 0.0);
       if (__syncthreads_or(bad) && !serial) {
         serial = true;
         if (t0 > 0 && tid == 0) {   // candles 1 .. t0 - 1 were all observations
@@ -441,12 +398,12 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
     }
     if (serial) {
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) sX[SG_K * tid + k] = c[k];
+      for (int k = 0; k < SG::K; ++k) sX[SG::K * tid + k] = c[k];
       __syncthreads();
       if (tid == 0) {
         double wg = sSt[0], wl = sSt[1], owt = sSt[2], prev = sSt[3];
         int nobs = sNobs;
-        const int n = min(SG_TT, T - t0);
+        const int n = min(SG::TT, T - t0);
         for (int i = 0; i < n; ++i) {
           const double cur = sX[i];
           const double d = cur - prev;
@@ -486,19 +443,19 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
         sNobs = nobs;
       }
       __syncthreads();
-      double rsi[SG_K];
+      double rsi[SG::K];
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) rsi[k] = sX[SG_K * tid + k];
-      sg_store(ro, tb, T, A.vout, rsi);
-      if (t0 + SG_TT >= T) break;
+      for (int k = 0; k < SG::K; ++k) rsi[k] = sX[SG::K * tid + k];
+      store_lines<SG::K>(ro, tb, T, A.vout, rsi);
+      if (t0 + SG::TT >= T) break;
       __syncthreads();
       continue;
     }
-    double g[SG_K], l[SG_K];
+    double g[SG::K], l[SG::K];
     {
       double pc = pc0;
 #pragma unroll
-      for (int k = 0; k < SG_K; ++k) {
+      for (int k = 0; k < SG::K; ++k) {
         const double d = c[k] - pc;
         g[k] = d != d ? d : (d > 0.0 ? d : 0.0);
         l[k] = d != d ? d : (d < 0.0 ? -d : 0.0);
@@ -509,7 +466,7 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
     // observation) resets the state: a = 0, b = x
     double A_ = 1.0, Bg = 0.0, Bl = 0.0;
 #pragma unroll
-    for (int k = 0; k < SG_K; ++k) {
+    for (int k = 0; k < SG::K; ++k) {
       const int t = tb + k;
       if (t == 0) continue;   // NaN observation before any: no state
       if (t == 1) {
@@ -553,9 +510,9 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
     yg = fma(ea, yg, eg);
     yl = fma(ea, yl, el);
     // exact replay of the lane's K steps
-    double rsi[SG_K];
+    double rsi[SG::K];
 #pragma unroll
-    for (int k = 0; k < SG_K; ++k) {
+    for (int k = 0; k < SG::K; ++k) {
       const int t = tb + k;
       if (t == 1) {
         yg = g[k];
@@ -571,10 +528,10 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
       }
       rsi[k] = v;
     }
-    sg_store(ro, tb, T, A.vout, rsi);
-    if (t0 + SG_TT >= T) break;
+    store_lines<SG::K>(ro, tb, T, A.vout, rsi);
+    if (t0 + SG::TT >= T) break;
     __syncthreads();
-    if (tid == SG_NT - 1) {
+    if (tid == SG::NT - 1) {
       sCarry[0] = yg;
       sCarry[1] = yl;
     }
@@ -584,15 +541,13 @@ __global__ __launch_bounds__(SG_NT) void wilder_rsi_kernel(const SigArgs A) {
 
 // 16-byte vector access needs every row start 16-byte aligned
 static void set_vec(SigArgs& A, int64_t ld_in, int64_t ld_out, int n_in) {
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15u) == 0; };
-  A.vin = (ld_in % 2) == 0;
-  for (int i = 0; i < n_in; ++i) A.vin &= al(A.in[i]);
-  A.vout = (ld_out % 2) == 0 && al(A.out);
+  A.vin = vec_rows(A.in, n_in, ld_in);
+  A.vout = vec_rows(&A.out, 1, ld_out);
 }
 
 static bool sig_ok(const void* a, int64_t S, int64_t T, int64_t ld_in, int64_t ld_out, const void* out, int w,
                    int wmax) {
-  return a && out && S >= 0 && T >= 0 && ld_in >= T && ld_out >= T && T <= 0x7fffffff - 2 * SG_TT &&
+  return a && out && S >= 0 && T >= 0 && ld_in >= T && ld_out >= T && T <= 0x7fffffff - 2 * SG::TT &&
          S <= 0x7fffffff && w >= 1 && w <= wmax;
 }
 
@@ -615,8 +570,8 @@ int bq_zscore(const double* close, int64_t S, int64_t T, int64_t ld_in, int32_t 
   A.win = window;
   A.inv_w = 1.0 / (double)window;
   set_vec(A, ld_in, ld_out, 1);
-  if (window == 20) hipLaunchKernelGGL(zscore_kernel<20>, dim3((unsigned)S), dim3(SG_NT), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(zscore_kernel<0>, dim3((unsigned)S), dim3(SG_NT), 0, (hipStream_t)stream, A);
+  if (window == 20) hipLaunchKernelGGL(zscore_kernel<20>, dim3((unsigned)S), dim3(SG::NT), 0, (hipStream_t)stream, A);
+  else hipLaunchKernelGGL(zscore_kernel<0>, dim3((unsigned)S), dim3(SG::NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
 
@@ -624,7 +579,7 @@ int bq_adx(const double* high, const double* low, const double* close, int64_t S
            int32_t window, double* out, int64_t ld_out, void* stream) {
   using namespace bq;
   // the mean of dx reaches 2 (w - 1) candles back: inside the 128-candle halo
-  if (!high || !low || !sig_ok(close, S, T, ld_in, ld_out, out, window, SG_H / 2)) return BQ_EINVAL;
+  if (!high || !low || !sig_ok(close, S, T, ld_in, ld_out, out, window, SG::H / 2)) return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
   SigArgs A;
   memset(&A, 0, sizeof A);
@@ -638,8 +593,8 @@ int bq_adx(const double* high, const double* low, const double* close, int64_t S
   A.win = window;
   A.inv_w = 1.0 / (double)window;
   set_vec(A, ld_in, ld_out, 3);
-  if (window == 14) hipLaunchKernelGGL(adx_kernel<14>, dim3((unsigned)S), dim3(SG_NT), 0, (hipStream_t)stream, A);
-  else hipLaunchKernelGGL(adx_kernel<0>, dim3((unsigned)S), dim3(SG_NT), 0, (hipStream_t)stream, A);
+  if (window == 14) hipLaunchKernelGGL(adx_kernel<14>, dim3((unsigned)S), dim3(SG::NT), 0, (hipStream_t)stream, A);
+  else hipLaunchKernelGGL(adx_kernel<0>, dim3((unsigned)S), dim3(SG::NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
 
@@ -663,9 +618,9 @@ int bq_wilder_rsi(const double* close, int64_t S, int64_t T, int64_t ld_in, int3
   A.den = A.om + A.alpha;
   set_vec(A, ld_in, ld_out, 1);
   if (A.den != 1.0)
-    hipLaunchKernelGGL(wilder_rsi_kernel<true>, dim3((unsigned)S), dim3(SG_NT), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(wilder_rsi_kernel<true>, dim3((unsigned)S), dim3(SG::NT), 0, (hipStream_t)stream, A);
   else
-    hipLaunchKernelGGL(wilder_rsi_kernel<false>, dim3((unsigned)S), dim3(SG_NT), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(wilder_rsi_kernel<false>, dim3((unsigned)S), dim3(SG::NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
 

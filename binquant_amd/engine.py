@@ -188,6 +188,19 @@ def _check_panel(x: torch.Tensor, name: str, shape=None) -> torch.Tensor:
     return x
 
 
+def _panels(tensors, names, S: int, T: int) -> list[torch.Tensor]:
+    """The tensors checked against (S, T) (_check_panel), contiguous."""
+    return [_check_panel(t, n, (S, T)).contiguous() for t, n in zip(tensors, names)]
+
+
+def _bench_rows(T: int, **rows) -> list[torch.Tensor]:
+    """The benchmark's rows (name=tensor) as contiguous [T] vectors."""
+    for n, t in rows.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.numel() != T:
+            raise ValueError(f"{n}: expected a float64 CUDA tensor of {T} values")
+    return [t.reshape(T).contiguous() for t in rows.values()]
+
+
 def _row_stride(x: torch.Tensor) -> int:
     return int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1])
 
@@ -376,16 +389,11 @@ def pump_features(
     then the kernel reads neither ema column back and returns it as given."""
     close = _check_panel(close, "close")
     S, T = close.shape
-    ins = [_check_panel(t, n, (S, T)).contiguous() for t, n in
-           zip((high, low, close, volume, candidate_atr, ema20, ema50),
-               ("high", "low", "close", "volume", "candidate_atr", "ema20", "ema50"))]
+    ins = _panels((high, low, close, volume, candidate_atr, ema20, ema50),
+                  ("high", "low", "close", "volume", "candidate_atr", "ema20", "ema50"), S, T)
     if trend_score is not None:
         trend_score = _check_panel(trend_score, "trend_score", (S, T))
-    bench = []
-    for t, n in zip((bench_ffill, bench_ema20, bench_ema50), ("bench_ffill", "bench_ema20", "bench_ema50")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.numel() != T:
-            raise ValueError(f"{n}: expected a float64 CUDA tensor of {T} values")
-        bench.append(t.reshape(T).contiguous())
+    bench = _bench_rows(T, bench_ffill=bench_ffill, bench_ema20=bench_ema20, bench_ema50=bench_ema50)
     given = {"candidate_atr": ins[4], "ema20": ins[5], "ema50": ins[6]}
     if trend_score is not None:
         given["trend_score"] = trend_score
@@ -422,13 +430,8 @@ def pump_features_ewm(
     column read back; liquidation_sweep_pump.py:206-217, 252-253)."""
     close = _check_panel(close, "close")
     S, T = close.shape
-    ins = [_check_panel(t, n, (S, T)).contiguous() for t, n in
-           zip((high, low, close, volume), ("high", "low", "close", "volume"))]
-    bench = []
-    for t, n in zip((bench_ffill, bench_ema20, bench_ema50), ("bench_ffill", "bench_ema20", "bench_ema50")):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or t.numel() != T:
-            raise ValueError(f"{n}: expected a float64 CUDA tensor of {T} values")
-        bench.append(t.reshape(T).contiguous())
+    ins = _panels((high, low, close, volume), ("high", "low", "close", "volume"), S, T)
+    bench = _bench_rows(T, bench_ffill=bench_ffill, bench_ema20=bench_ema20, bench_ema50=bench_ema50)
     out = {n: torch.empty((S, T), dtype=torch.float64, device=close.device) for n in PUMP_COLUMNS}
     st = _lib.load().bq_pump_features_ewm(
         _lib.ptr_array([t.data_ptr() for t in ins]), S, T, T, _lib.ptr_array([t.data_ptr() for t in bench]),
@@ -545,6 +548,34 @@ def _cols(S, T, dev, names, dtype, given=None):
     return {n: given[n] if n in given else torch.empty((S, T), dtype=dtype, device=dev) for n in names}
 
 
+# bq_spike_base_std's std columns (enum bq_spike_std_col), under their
+# FailedSpikeFade.detect names
+SPIKE_STD = ("price_std", "volume_std", "rolling_price_std_8", "rolling_price_std_20", "body_size_pct_std_10")
+
+
+def _spike_base(entry: str, ins, names, base_window, streak_length, body_size_pct, stream) -> dict[str, torch.Tensor]:
+    """spike_base / spike_base_std: ins[3] is the close; bq_spike_base_std also
+    writes (and returns) the SPIKE_STD columns."""
+    c = _check_panel(ins[3], "c")
+    S, T = c.shape
+    ins = _panels(ins, names, S, T)
+    out = _cols(S, T, c.device, SPIKE_BASE_FLOAT, torch.float64,
+                {"body_size_pct": body_size_pct} if body_size_pct is not None else None)
+    flags = _cols(S, T, c.device, SPIKE_BASE_BOOL, torch.bool)
+    sd = _cols(S, T, c.device, SPIKE_STD, torch.float64) if entry == "bq_spike_base_std" else {}
+    st = getattr(_lib.load(), entry)(
+        _lib.ptr_array([t.data_ptr() for t in ins]), S, T, T, int(base_window), int(streak_length),
+        _lib.ptr_array([0 if (n == "body_size_pct" and body_size_pct is not None) else out[n].data_ptr()
+                        for n in SPIKE_BASE_FLOAT]),
+        _lib.ptr_array([flags[n].data_ptr() for n in SPIKE_BASE_BOOL]),
+        *([_lib.ptr_array([sd[n].data_ptr() for n in SPIKE_STD])] if sd else []), T, _stream_handle(stream),
+    )
+    _lib.check(st, entry)
+    out.update(flags)
+    out.update(sd)
+    return out
+
+
 @device_entry
 def spike_base(o, h, l, c, v, qv, close_ffill, price_std, volume_std, std8, std20, body_pct_std, base_window: int = 12,
                streak_length: int = 3, body_size_pct: torch.Tensor | None = None,
@@ -553,28 +584,10 @@ def spike_base(o, h, l, c, v, qv, close_ffill, price_std, volume_std, std8, std2
     (strategies/failed_spike_fade.py:260-357) in one pass per row
     (bq_spike_base), given the ffilled close and the rolling std columns;
     body_size_pct: an existing column with the kernel's values (not rewritten)."""
-    c = _check_panel(c, "c")
-    S, T = c.shape
-    ins = [_check_panel(t, n, (S, T)).contiguous() for t, n in zip(
-        (o, h, l, c, v, qv, close_ffill, price_std, volume_std, std8, std20, body_pct_std),
-        ("o", "h", "l", "c", "v", "qv", "close_ffill", "price_std", "volume_std", "std8", "std20", "body_pct_std"))]
-    out = _cols(S, T, c.device, SPIKE_BASE_FLOAT, torch.float64,
-                {"body_size_pct": body_size_pct} if body_size_pct is not None else None)
-    flags = _cols(S, T, c.device, SPIKE_BASE_BOOL, torch.bool)
-    st = _lib.load().bq_spike_base(
-        _lib.ptr_array([t.data_ptr() for t in ins]), S, T, T, int(base_window), int(streak_length),
-        _lib.ptr_array([0 if (n == "body_size_pct" and body_size_pct is not None) else out[n].data_ptr()
-                        for n in SPIKE_BASE_FLOAT]),
-        _lib.ptr_array([flags[n].data_ptr() for n in SPIKE_BASE_BOOL]), T, _stream_handle(stream),
-    )
-    _lib.check(st, "bq_spike_base")
-    out.update(flags)
-    return out
-
-
-# bq_spike_base_std's std columns (enum bq_spike_std_col), under their
-# FailedSpikeFade.detect names
-SPIKE_STD = ("price_std", "volume_std", "rolling_price_std_8", "rolling_price_std_20", "body_size_pct_std_10")
+    return _spike_base(
+        "bq_spike_base", (o, h, l, c, v, qv, close_ffill, price_std, volume_std, std8, std20, body_pct_std),
+        ("o", "h", "l", "c", "v", "qv", "close_ffill", "price_std", "volume_std", "std8", "std20", "body_pct_std"),
+        base_window, streak_length, body_size_pct, stream)
 
 
 @device_entry
@@ -586,25 +599,9 @@ def spike_base_std(o, h, l, c, v, qv, close_ffill, base_window: int = 12, streak
     window sums — the window's variance to rounding, where pandas' online
     recurrence (and its bit-exact replay, spike_base's inputs) drifts — and
     returned beside the base columns under their detect() names."""
-    c = _check_panel(c, "c")
-    S, T = c.shape
-    ins = [_check_panel(t, n, (S, T)).contiguous() for t, n in zip(
-        (o, h, l, c, v, qv, close_ffill), ("o", "h", "l", "c", "v", "qv", "close_ffill"))]
-    out = _cols(S, T, c.device, SPIKE_BASE_FLOAT, torch.float64,
-                {"body_size_pct": body_size_pct} if body_size_pct is not None else None)
-    flags = _cols(S, T, c.device, SPIKE_BASE_BOOL, torch.bool)
-    sd = _cols(S, T, c.device, SPIKE_STD, torch.float64)
-    st = _lib.load().bq_spike_base_std(
-        _lib.ptr_array([t.data_ptr() for t in ins]), S, T, T, int(base_window), int(streak_length),
-        _lib.ptr_array([0 if (n == "body_size_pct" and body_size_pct is not None) else out[n].data_ptr()
-                        for n in SPIKE_BASE_FLOAT]),
-        _lib.ptr_array([flags[n].data_ptr() for n in SPIKE_BASE_BOOL]),
-        _lib.ptr_array([sd[n].data_ptr() for n in SPIKE_STD]), T, _stream_handle(stream),
-    )
-    _lib.check(st, "bq_spike_base_std")
-    out.update(flags)
-    out.update(sd)
-    return out
+    return _spike_base("bq_spike_base_std", (o, h, l, c, v, qv, close_ffill),
+                       ("o", "h", "l", "c", "v", "qv", "close_ffill"), base_window, streak_length, body_size_pct,
+                       stream)
 
 
 _SPIKE_MODES = {"last": 0, "first": 1, "all": 2}
@@ -621,8 +618,8 @@ def spike_flags(o, c, close_ffill, volume_ratio, dyn_threshold, vcmr, pbbt, para
     take both as [2S, T] rows)."""
     c = _check_panel(c, "c")
     S, T = c.shape
-    ins = [_check_panel(t, n, (S, T)).contiguous() for t, n in zip(
-        (o, c, close_ffill, volume_ratio, dyn_threshold), ("o", "c", "close_ffill", "volume_ratio", "dyn_threshold"))]
+    ins = _panels((o, c, close_ffill, volume_ratio, dyn_threshold),
+                  ("o", "c", "close_ffill", "volume_ratio", "dyn_threshold"), S, T)
     vc = vcmr.reshape(S).contiguous().to(torch.float64)
     pb = pbbt.reshape(S).contiguous().to(torch.float64)
     pr = _lib.BqSpikeParams(int(params.volume_cluster_window), int(params.volume_cluster_min_count),
@@ -841,7 +838,7 @@ class TickState:
             raise ValueError(f"seed panel has {S} symbols, state has {self.n_symbols}")
         if close.device != self.device:
             raise ValueError(f"seed panel on {close.device}, state on {self.device}")
-        ins = [_check_panel(t, n, (S, T)).contiguous() for t, n in zip((open_, high, low, close, volume), INPUT_FIELDS)]
+        ins = _panels((open_, high, low, close, volume), INPUT_FIELDS, S, T)
         st = self._lib.bq_state_seed(
             self._h, _lib.ptr_array([t.data_ptr() for t in ins]), T, T, _stream_handle(stream)
         )
