@@ -194,6 +194,21 @@ IMPULSE_VALUES = ("impulse_return_1h", "previous_impulse_return_1h", "btc_return
                   "trigger_return_15m", "confirmation_return_15m", "confirmation_close_location", "atr_pct",
                   "entry_limit_price")
 
+
+class BqRetestParams(ctypes.Structure):
+    """Mirror of ``bq_retest_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("watch_ms", ctypes.c_int64), ("min_history", ctypes.c_int32), ("breakout_lookback", ctypes.c_int32),
+                ("support_factor", ctypes.c_double), ("pullback_factor", ctypes.c_double)]
+
+
+# bq_retest_replay: event codes (BQ_RT_*), detail bits (BQ_RT_D_*)
+RETEST_MAX_LOOKBACK = 64
+(BQ_RT_IDLE, BQ_RT_WATCH_SET, BQ_RT_WATCHING, BQ_RT_RISK_BLOCKED, BQ_RT_CANDIDATE, BQ_RT_SHORT_HISTORY) = range(6)
+BQ_RT_NO_FRAME = 255
+BQ_RT_D_SUPPORT, BQ_RT_D_PULLBACK, BQ_RT_D_RECLAIM, BQ_RT_D_EXPIRED = 1, 2, 4, 8
+RT_EVENTS = ("idle", "watch_set", "watching", "risk_blocked", "candidate", "history_too_short")
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
@@ -236,6 +251,9 @@ SIGNATURES: dict[str, tuple] = {
     "bq_impulse_rider": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _P, _P, _I64,
                                         ctypes.POINTER(BqImpulseParams), _P, _PP, _I64, _P]),
     "bq_bb_stable": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, ctypes.c_double, _P, _P, _I64, _P]),
+    "bq_retest_default_params": (None, [ctypes.POINTER(BqRetestParams)]),
+    "bq_retest_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                        ctypes.POINTER(BqRetestParams), _P, _P, _P, _P, _P, _P, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

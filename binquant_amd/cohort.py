@@ -65,7 +65,8 @@ def _side_streams(device: torch.device, n: int) -> list[torch.cuda.Stream]:
 
 def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, btc_c15,
                    max_bars: int = 400, exact: bool = True, h1_max_bins: int | None = None,
-                   gates: bool = False) -> dict[str, torch.Tensor]:
+                   gates: bool = False, retest: signals.RetestState | None = None,
+                   retest_risk: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -80,8 +81,15 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     signals.IR_KEYS and impulse.status, from the 15m panel, e15.ATR and
     ts15 / btc_ts15 / btc_c15; context_evaluator.py:446-454) and of the grid
     ladder (ladder.stable / ladder.change_pct from e15.bb_*); the default
-    leaves the returned dict and the launch sequence as they were. Returns a
-    flat dict of tensors (names prefixed by the stage)."""
+    leaves the returned dict and the launch sequence as they were. retest: the
+    cohort's GradualGainerRetest watchlist (signals.RetestState, [S]): the
+    body of its signal() (:222-308 of the strategy) runs on the newest 15m
+    candle, after the leadership and on its stream, from that state, which is
+    updated in place (a captured graph carries it from message to message);
+    retest.event / retest.detail / retest.breakout_level [S] are added.
+    retest_risk: _risk_allows for that candle, bool [S] (or [S, T15]; None:
+    allowed). Without a state the outputs and launches are unchanged. Returns
+    a flat dict of tensors (names prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -136,8 +144,18 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
         out["top.status"] = status
 
     def lead(out):
-        for k, v in signals.gradual_gainer_leadership(ts15, c15, btc_ts15, btc_c).items():
+        res = signals.gradual_gainer_leadership(ts15, c15, btc_ts15, btc_c)
+        for k, v in res.items():
             out[f"lead.{k}"] = v
+        if retest is not None:   # signal()'s body on the cohort's message: the newest candle only
+            risk = retest_risk
+            if risk is not None and risk.dim() == 1:
+                risk = risk.reshape(S, 1).expand(S, T15)
+            newest = torch.full((S,), T15 - 1, dtype=torch.int64, device=c15.device)
+            rt = signals.gradual_gainer_retest(o15, h15, l15, c15, ts15, btc_ts15, btc_c, risk_ok=risk, state=retest,
+                                               from_t=newest, leadership=res)
+            out["retest.event"], out["retest.detail"] = rt["event"][:, -1], rt["detail"][:, -1]
+            out["retest.breakout_level"] = rt["breakout_level"][:, -1]
 
     order = (frame_5m, frame_15m, context, pump, spike, top, lead)
     parts = {f: {} for f in order}

@@ -1518,6 +1518,86 @@ def bb_stable(bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tens
     return stable, chg
 
 
+RETEST_DEFAULTS = dict(   # GradualGainerRetest's class attributes (:78-85)
+    watch_ms=8 * 3_600_000, min_history=100, breakout_lookback=8, support_factor=1 - 0.5 / 100,
+    pullback_factor=1 - 0.04)
+
+
+@device_entry
+def retest_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Tensor, ema: torch.Tensor,
+                  open_time: torch.Tensor, leader: torch.Tensor, risk_ok: torch.Tensor | None = None, *,
+                  state=None, first_t=None, lens=None, from_t=None, detail: bool = True, level: bool = True,
+                  **params):
+    """GradualGainerRetest.signal()'s watchlist state machine replayed over
+    the panel (strategies/gradual_gainer_retest.py:222-308; bq_retest_replay):
+    column t of row s = the method on the message whose frame is
+    df.iloc[first_t[s]:t + 1], after the messages of all earlier candles;
+    candles from_t[s] .. lens[s] - 1 are replayed. Panels [S, T] float64 with
+    unit stride along T and any row pitch (ema: the frame's EMA20 column, read
+    at t - 1), open_time [S, T] int64 ms, strictly ascending within a row's
+    frame; leader / risk_ok [S, T] bool (risk_ok None: always allowed).
+    state: None (start idle, discard) or the (active uint8, started int64,
+    level float64) [S] tensors, updated in place. Returns (event uint8,
+    detail uint8 or None, level float64 or None), each [S, T] (_lib.BQ_RT_*).
+    params: RETEST_DEFAULTS' keys (the two factors formed in Python floats)."""
+    bad = set(params) - set(RETEST_DEFAULTS)
+    if bad:
+        raise ValueError(f"retest_replay: unknown parameters {sorted(bad)} (known: {sorted(RETEST_DEFAULTS)})")
+    par = {**RETEST_DEFAULTS, **params}
+    L, mh = int(par["breakout_lookback"]), int(par["min_history"])
+    if not 1 <= L <= _lib.RETEST_MAX_LOOKBACK or L >= mh:
+        raise ValueError(f"retest_replay: breakout_lookback must be in 1..{_lib.RETEST_MAX_LOOKBACK} and below "
+                         f"min_history ({mh}), got {L}")
+    if int(par["watch_ms"]) < 0:
+        raise ValueError("retest_replay: watch_ms must be >= 0")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    for x, name in ((o, "open"), (h, "high"), (l, "low"), (c, "close"), (ema, "ema")):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
+        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
+    for x, name in ((leader, "leader"), (risk_ok, "risk_ok")):
+        if x is None and name == "risk_ok":
+            continue
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.bool or tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)}")
+    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
+        _gate_rows(from_t, "from_t", S)
+    if state is not None:
+        if len(state) != 3:
+            raise ValueError("state: expected (active, started, level)")
+        for x, name, dt in zip(state, ("state.active", "state.started", "state.level"),
+                               (torch.uint8, torch.int64, torch.float64)):
+            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in ((o, "open"), (h, "high"), (l, "low"), (c, "close"),
+                                                                 (ema, "ema"))])
+    ts = _check_ts(open_time, "open_time")
+    flags = [leader] if risk_ok is None else [leader, risk_ok]
+    if not all(x.is_cuda for x in flags + list(state or ())):
+        raise ValueError("leader / risk_ok / state: expected CUDA tensors (no CPU path)")
+    if any(f.shape[1] > 1 and f.stride(1) != 1 for f in flags):
+        flags = [f.contiguous() for f in flags]
+    flags, ld_b = _common_pitch(flags)
+    dev = c.device
+    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    p = _lib.BqRetestParams(int(par["watch_ms"]), mh, L, float(par["support_factor"]), float(par["pullback_factor"]))
+    event = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    det = torch.empty((S, T), dtype=torch.uint8, device=dev) if detail else None
+    lvl = torch.empty((S, T), dtype=torch.float64, device=dev) if level else None
+    sa, ss, sl = state if state is not None else (None, None, None)
+    st = _lib.load().bq_retest_replay(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), ld_in,
+                                      _ptr(ts), T, _ptr(flags[0]), _ptr(flags[1] if risk_ok is not None else None),
+                                      ld_b, _ptr(lens), _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(sa),
+                                      _ptr(ss), _ptr(sl), _ptr(event), _ptr(det), _ptr(lvl), T, _stream_handle(None))
+    _lib.check(st, "bq_retest_replay")
+    return event, det, lvl
+
+
 def _join_capacity(ts: torch.Tensor, lens: torch.Tensor | None, bts: torch.Tensor) -> int:
     """Largest per-row count of (candle, benchmark row) matches over the
     candles t >= 1 that join (bench_ts ascending): an upper bound on every

@@ -22,6 +22,10 @@ prefix frame df.iloc[:t + 1]:
                      pass (bq_impulse.hip)
 * bb_width_stable    LadderDeployer._bb_stable (strategies/grid/ladder_deployer.py:42-56),
                      one pass (bq_impulse.hip)
+* gradual_gainer_retest    the body of GradualGainerRetest.signal()
+                     (strategies/gradual_gainer_retest.py:222-308): the watchlist
+                     state machine replayed per row (bq_retest.hip), with
+                     retest_risk_allows for _risk_allows (:198-215)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -253,6 +257,100 @@ def gradual_gainer_leadership(open_time: torch.Tensor, close: torch.Tensor, btc_
     leader = strengths & ~F.isnan(T2) & (R2 > 0) & (R6 > 0) & (R2 >= T2) & (R6 >= T6)
     res = F.run({"leader": leader, "rs_2h": F.where(strengths, R2, 0.0), "rs_6h": F.where(strengths, R6, 0.0)}, S, T)
     return res
+
+
+# GradualGainerRetest.signal()'s per-candle outcome, as uint8 codes
+# (bq_retest_replay's BQ_RT_*), and the detail bits beside them
+(RT_IDLE, RT_WATCH_SET, RT_WATCHING, RT_RISK_BLOCKED, RT_CANDIDATE, RT_SHORT_HISTORY) = range(6)
+RT_NO_FRAME = _lib.BQ_RT_NO_FRAME   # t < from_t[s] or t >= lens[s]: no message replayed
+RT_EVENTS = dict(enumerate(_lib.RT_EVENTS))
+RT_D_SUPPORT, RT_D_PULLBACK, RT_D_RECLAIM, RT_D_EXPIRED = (_lib.BQ_RT_D_SUPPORT, _lib.BQ_RT_D_PULLBACK,
+                                                          _lib.BQ_RT_D_RECLAIM, _lib.BQ_RT_D_EXPIRED)
+
+
+class RetestState:
+    """The watchlist of GradualGainerRetest for S rows (its strategy_states
+    entries): active uint8, started int64 (ms; expires_at = started +
+    watch_ms), level float64 (the breakout level), each [S] on the device.
+    signals.gradual_gainer_retest / engine.retest_replay update it in place,
+    so a captured graph carries it from one replay to the next."""
+
+    __slots__ = ("active", "started", "level")
+
+    def __init__(self, active: torch.Tensor, started: torch.Tensor, level: torch.Tensor):
+        self.active, self.started, self.level = active, started, level
+
+    @classmethod
+    def idle(cls, S: int, device) -> "RetestState":
+        return cls(torch.zeros(S, dtype=torch.uint8, device=device), torch.zeros(S, dtype=torch.int64, device=device),
+                   torch.full((S,), NAN, dtype=torch.float64, device=device))
+
+    def tensors(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.active, self.started, self.level
+
+
+def gradual_gainer_retest(o, h, l, c, open_time, btc_time, btc_close, *, risk_ok=None, state: RetestState | None = None,
+                          first_t=None, lens=None, from_t=None, leadership=None, ema20=None, **params):
+    """The body of GradualGainerRetest.signal() (strategies/gradual_gainer_retest.py
+    :222-308) for every candle of the panel: the leadership (unless given:
+    gradual_gainer_leadership's dict), the frame's EMA20 (unless given) and
+    the watchlist replay (engine.retest_replay, bq_retest_replay). Column t of
+    row s = the method on the message whose frame is df.iloc[first_t[s]:t + 1],
+    after the messages of all earlier candles; candles from_t[s] ..
+    lens[s] - 1 are replayed, from `state` (None: idle), which is updated in
+    place. risk_ok [S, T] bool: _risk_allows per candle (retest_risk_allows;
+    None: always allowed). open_time ascends strictly within a row's frame.
+
+    The leadership and the EMA computed here are the whole row's: for rows
+    with first_t > 0 pass `leadership` / `ema20` of the trimmed frame (or the
+    trimmed row itself). params: engine.RETEST_DEFAULTS' keys.
+
+    Returns {"event": uint8 [S, T] (RT_* codes, RT_EVENTS their names),
+    "detail": uint8 [S, T] (RT_D_* bits: the failed tests of a watching
+    candle; RT_D_EXPIRED where the watch expired on this candle),
+    "breakout_level": [S, T] (the level in force at watch_set / watching /
+    risk_blocked / candidate candles, NaN elsewhere), "leader", "rs_2h",
+    "rs_6h", "ema20"}."""
+    lead = leadership if leadership is not None else gradual_gainer_leadership(open_time, c, btc_time, btc_close)
+    e20 = ema20 if ema20 is not None else ema(c, 20)
+    event, detail, level = engine.retest_replay(o, h, l, c, e20, open_time, lead["leader"], risk_ok,
+                                                state=state.tensors() if state is not None else None,
+                                                first_t=first_t, lens=lens, from_t=from_t, **params)
+    return {"event": event, "detail": detail, "breakout_level": level, "leader": lead["leader"],
+            "rs_2h": lead["rs_2h"], "rs_6h": lead["rs_6h"], "ema20": e20}
+
+
+# GradualGainerRetest._risk_allows' reasons (:198-215), as uint8 codes: the first failing check in the method's order
+RISK_REASONS = ("risk_profile_allows_long", "market_context_unavailable", "market_stress_too_high", "btc_context_down",
+                "symbol_regime_unavailable", "symbol_atr_too_high", "symbol_transition_not_long", "symbol_trend_down")
+
+
+def retest_risk_allows(market_stress_score, btc_regime_score, btc_return, context_ok, atr_pct, micro_regime,
+                       micro_transition, trend_score, features_ok, max_market_stress: float = 0.25,
+                       max_atr_pct: float = 0.06):
+    """GradualGainerRetest._risk_allows (strategies/gradual_gainer_retest.py:198-215)
+    per (symbol, candle): the context's market_stress_score / btc_regime_score
+    / btc_return [T] float64 and context_ok [T] bool (False: no context), the
+    symbol features atr_pct / trend_score [S, T] float64, micro_regime /
+    micro_transition [S, T] int8 (_lib.MICRO_REGIMES / MICRO_TRANSITIONS
+    codes, negative: none) and features_ok [S, T] bool (False: the context
+    has no features for the symbol). Returns (ok bool [S, T], reason uint8
+    [S, T]): the first failing check in the method's order, RISK_REASONS its
+    strings (0 = risk_profile_allows_long). One fused element-wise program."""
+    S, T = atr_pct.shape
+    down, breakdown, entered_down = (float(_lib.MICRO_REGIMES.index("TREND_DOWN")),
+                                     float(_lib.MICRO_TRANSITIONS.index("BREAKDOWN")),
+                                     float(_lib.MICRO_TRANSITIONS.index("ENTERED_TREND_DOWN")))
+    STRESS, REG, RET = F.inp(market_stress_score), F.inp(btc_regime_score), F.inp(btc_return)
+    ATR, TREND = F.inp(atr_pct), F.inp(trend_score)
+    MR, MT = F.inp(micro_regime.to(torch.float64)), F.inp(micro_transition.to(torch.float64))
+    checks = [~F.inp(context_ok), STRESS >= max_market_stress, (REG < -0.2) & (RET < 0.0), ~F.inp(features_ok),
+              ATR > max_atr_pct, (MT == breakdown) | (MT == entered_down), (MR == down) & (TREND < 0.0)]
+    code = F.const(0.0)
+    for i in range(len(checks), 0, -1):
+        code = F.where(checks[i - 1], float(i), code)
+    reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
+    return reason == 0, reason
 
 
 # RelativeStrengthImpulseRider._features reason strings, as uint8 codes

@@ -49,6 +49,8 @@
  *                         (strategies/relative_strength_impulse_rider.py:69-198)
  *   bq_bb_stable       <- LadderDeployer._bb_stable
  *                         (strategies/grid/ladder_deployer.py:42-56)
+ *   bq_retest_replay   <- GradualGainerRetest.signal()'s watchlist state machine
+ *                         (strategies/gradual_gainer_retest.py:222-308)
  *   bq_breadth_partial <- the per-symbol sums/counts of
  *                         LiveMarketContextAccumulator._build_context
  *                         market_regime/live_market_context_accumulator.py:135-163
@@ -316,6 +318,66 @@ int bq_leadership(const int64_t* open_time, int64_t ld_ts, const double* close, 
                   double rs_quantile, int32_t lookback, int32_t min_history, int32_t min_count,
                   int32_t short_bars, int32_t long_bars, void* workspace, size_t workspace_bytes,
                   uint8_t* leader, double* rs_2h, double* rs_6h, int64_t ld_out, void* stream);
+
+/*
+ * GradualGainerRetest.signal()'s watchlist state machine replayed over a panel
+ * (strategies/gradual_gainer_retest.py:222-308): column t of row s is what
+ * signal() does on the message whose frame is df.iloc[first:t + 1], first =
+ * first_t[s] (NULL: 0), after the messages of all earlier candles of the row.
+ * Candles t = from_t[s] (NULL: 0) .. lens[s] - 1 (NULL: T) are replayed.
+ * open / high / low / close / ema [S][ld_in] (ema: the frame's
+ * close.ewm(span=20, adjust=False).mean() column, read at t - 1), open_time
+ * [S][ld_ts] int64 ms, leader (bq_leadership's output) and risk_ok (NULL: the
+ * risk check always allows) [S][ld_b] 0 / 1 bytes.
+ *
+ * Per-row state: active, started_at (ms), breakout_level; expires_at is
+ * started_at + watch_ms (:119-125). Per candle, in the method's order:
+ *   t + 1 - first < min_history       -> SHORT_HISTORY, state untouched (:228-235)
+ *   active and open_time > expires_at -> the watch is cleared, D_EXPIRED (:239-241)
+ *   idle and leader[t]                -> WATCH_SET: started_at = open_time[t], level =
+ *                                        max(high[t-L .. t-1]) skipping NaN (:244-251)
+ *   idle                              -> IDLE (:252-253)
+ *   a watch in force: support = low[t-1] >= level * sf or low[t-1] >= ema[t-1] * sf,
+ *   pullback = close[t-1] >= level * pf, reclaim = close[t] > open[t] and
+ *   close[t] > high[t-1] (:255-268); any false -> WATCHING (the failed ones as
+ *   D_SUPPORT / D_PULLBACK / D_RECLAIM), all true and risk_ok[t] false ->
+ *   RISK_BLOCKED (:271-274), else CANDIDATE and the watch is cleared (:308).
+ * Every test is one correctly rounded fp64 multiply and a compare in the
+ * method's direction (a NaN fails it): events, details and levels are exact.
+ *
+ * Domain: open_time strictly ascending within [first, lens) — the
+ * strategy_cooldowns check (:275-282) fires only when two messages carry the
+ * same open_time and is not built. rank_score, the market-type check and
+ * _submit_candidate's message are the caller's.
+ *
+ * st_active / st_started / st_level [S]: read, then written in place with the
+ * state after the row's last replayed candle (a captured graph replays the
+ * call as it replays the tick state); all three NULL: start idle, discard.
+ * event [S][ld_out] bytes (BQ_RT_*; NO_FRAME where t < from_t or t >= lens),
+ * detail [S][ld_out] bytes (NULL = skip), level [S][ld_out] (NULL = skip): the
+ * level in force at WATCH_SET / WATCHING / RISK_BLOCKED / CANDIDATE candles,
+ * NaN elsewhere. params NULL: the class attributes (bq_retest_default_params).
+ * BQ_EINVAL unless 1 <= breakout_lookback <= BQ_RETEST_MAX_LOOKBACK and
+ * breakout_lookback < min_history (the level's window stays inside the frame).
+ * No workspace, nothing allocated.
+ */
+#define BQ_RETEST_MAX_LOOKBACK 64
+typedef struct bq_retest_params {
+  int64_t watch_ms;                         /* WATCHLIST_HOURS * 3_600_000 */
+  int32_t min_history, breakout_lookback;   /* MIN_HISTORY 100, BREAKOUT_LOOKBACK 8 */
+  double support_factor, pullback_factor;   /* 1 - SUPPORT_TOLERANCE_PCT / 100, 1 - MAX_PULLBACK_PCT, formed by
+                                               the caller in fp64 */
+} bq_retest_params;
+enum { BQ_RT_IDLE = 0, BQ_RT_WATCH_SET, BQ_RT_WATCHING, BQ_RT_RISK_BLOCKED, BQ_RT_CANDIDATE,
+       BQ_RT_SHORT_HISTORY, BQ_RT_NO_FRAME = 255 };
+enum { BQ_RT_D_SUPPORT = 1, BQ_RT_D_PULLBACK = 2, BQ_RT_D_RECLAIM = 4, BQ_RT_D_EXPIRED = 8 };
+void bq_retest_default_params(bq_retest_params* p);
+int bq_retest_replay(const double* open, const double* high, const double* low, const double* close,
+                     const double* ema, int64_t ld_in, const int64_t* open_time, int64_t ld_ts,
+                     const uint8_t* leader, const uint8_t* risk_ok, int64_t ld_b, const int64_t* lens,
+                     const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
+                     const bq_retest_params* params, uint8_t* st_active, int64_t* st_started, double* st_level,
+                     uint8_t* event, uint8_t* detail, double* level, int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t
