@@ -209,6 +209,40 @@ BQ_RT_NO_FRAME = 255
 BQ_RT_D_SUPPORT, BQ_RT_D_PULLBACK, BQ_RT_D_RECLAIM, BQ_RT_D_EXPIRED = 1, 2, 4, 8
 RT_EVENTS = ("idle", "watch_set", "watching", "risk_blocked", "candidate", "history_too_short")
 
+
+
+class BqTopGainerParams(ctypes.Structure):
+    """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("lookback_high", ctypes.c_int32), ("volume_window", ctypes.c_int32), ("min_history", ctypes.c_int32),
+                ("full_extension_bars", ctypes.c_int32), ("min_candle_return", ctypes.c_double),
+                ("max_candle_return", ctypes.c_double), ("min_return_1h", ctypes.c_double),
+                ("min_return_2h", ctypes.c_double), ("min_return_6h", ctypes.c_double),
+                ("max_return_1h", ctypes.c_double), ("max_extension", ctypes.c_double),
+                ("min_short_extension_cap", ctypes.c_double), ("min_volume_ratio", ctypes.c_double),
+                ("min_range_position", ctypes.c_double), ("max_upper_wick", ctypes.c_double),
+                ("atr_stop_mult", ctypes.c_double), ("min_stop_loss_pct", ctypes.c_double),
+                ("max_stop_loss_pct", ctypes.c_double)]
+
+
+# bq_top_gainer_entry: entry / status codes (BQ_TGE_*, the index is the code),
+# value-column order (_features' key order), the ring's halo
+TGE_MAX_LOOKBACK = 96
+TGE_REASONS = ("top_gainer_breakout_two_close_confirmation", "history_too_short", "invalid_candle_values",
+               "indicators_not_ready", "not_breaking_recent_high", "not_above_ema20_and_ema50",
+               "candle_not_green_enough", "single_candle_too_extended", "one_hour_move_too_extended",
+               "extension_move_too_extended", "momentum_not_accelerating", "six_hour_move_not_confirmed",
+               "volume_ratio_too_low", "close_not_near_high", "upper_wick_too_large",
+               "first_confirmation_did_not_hold_breakout", "second_confirmation_did_not_clear_breakout_close",
+               "risk_rejected")
+TGE_ENTRY_OK = "top_gainer_breakout_ignition"   # code 0 of the `entry` column (status 0: TGE_REASONS[0])
+BQ_TGE_CONFIRMED, BQ_TGE_SHORT_HISTORY, BQ_TGE_INVALID_CANDLE, BQ_TGE_NOT_READY = 0, 1, 2, 3
+BQ_TGE_FIRST_CONFIRM, BQ_TGE_SECOND_CONFIRM, BQ_TGE_RISK_REJECTED = 15, 16, 17
+TGE_NO_FRAME = BQ_TGE_NO_FRAME = 255
+TGE_VALUES = ("close", "open", "high", "low", "volume", "quote_volume", "previous_high", "return_1h", "return_2h",
+              "return_6h", "extension_return", "extension_window_bars", "extension_cap", "candle_return",
+              "volume_ratio", "quote_volume_ratio", "range_position", "upper_wick_fraction", "ema20", "ema50", "atr")
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
@@ -251,6 +285,9 @@ SIGNATURES: dict[str, tuple] = {
     "bq_impulse_rider": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _P, _P, _I64,
                                         ctypes.POINTER(BqImpulseParams), _P, _PP, _I64, _P]),
     "bq_bb_stable": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, ctypes.c_double, _P, _P, _I64, _P]),
+    "bq_top_gainer_default_params": (None, [ctypes.POINTER(BqTopGainerParams)]),
+    "bq_top_gainer_entry": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64,
+                                           ctypes.POINTER(BqTopGainerParams), _P, _P, _P, _P, _PP, _I64, _P]),
     "bq_retest_default_params": (None, [ctypes.POINTER(BqRetestParams)]),
     "bq_retest_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                         ctypes.POINTER(BqRetestParams), _P, _P, _P, _P, _P, _P, _I64, _P]),

@@ -66,7 +66,8 @@ def _side_streams(device: torch.device, n: int) -> list[torch.cuda.Stream]:
 def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, btc_c15,
                    max_bars: int = 400, exact: bool = True, h1_max_bins: int | None = None,
                    gates: bool = False, retest: signals.RetestState | None = None,
-                   retest_risk: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+                   retest_risk: torch.Tensor | None = None, top_entry: bool = False,
+                   top_risk: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -88,8 +89,15 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     updated in place (a captured graph carries it from message to message);
     retest.event / retest.detail / retest.breakout_level [S] are added.
     retest_risk: _risk_allows for that candle, bool [S] (or [S, T15]; None:
-    allowed). Without a state the outputs and launches are unchanged. Returns
-    a flat dict of tensors (names prefixed by the stage)."""
+    allowed). Without a state the outputs and launches are unchanged.
+    top_entry=True adds, after the 15m frame and on its stream,
+    TopGainerEarlyMomentum's decisions for every candle (signals.top_gainer_entry
+    on the 15m panel, v15 * c15 and e15.ATR, as the top stage reads them):
+    topentry.status / topentry.entry (uint8 [S, T15]) and topentry.score /
+    topentry.stop_loss_pct (unrounded). top_risk: _risk_profile_allows per
+    candle, bool [S, T15] (or [S]; None: allowed). The default leaves the
+    returned dict and the launch sequence as they were. Returns a flat dict of
+    tensors (names prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -122,6 +130,14 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
             out["impulse.status"] = status
             for k, v in signals.bb_width_stable(out["e15.bb_upper"], out["e15.bb_mid"], out["e15.bb_lower"]).items():
                 out[f"ladder.{k}"] = v
+        if top_entry:   # TopGainerEarlyMomentum.signal() (:363-406 of the strategy) at every candle
+            risk = top_risk
+            if risk is not None and risk.dim() == 1:
+                risk = risk.reshape(S, 1).expand(S, T15)
+            te = signals.top_gainer_entry(o15, h15, l15, c15, v15, v15 * c15, out["e15.ATR"], risk_ok=risk,
+                                          columns=())
+            for k in ("status", "entry", "score", "stop_loss_pct"):
+                out[f"topentry.{k}"] = te[k]
 
     def context(out):   # klines_provider.py:181-199
         part, last = engine.context_partials(h15, l15, c15, max_bars=max_bars, last=True)

@@ -1518,6 +1518,88 @@ def bb_stable(bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tens
     return stable, chg
 
 
+TOP_GAINER_DEFAULTS = dict(   # TopGainerEarlyMomentum's class attributes (:42-57, :64-66)
+    lookback_high=48, volume_window=32, min_history=56, full_extension_bars=96, min_candle_return=0.01,
+    max_candle_return=0.10, min_return_1h=0.05, min_return_2h=0.08, min_return_6h=0.07, max_return_1h=0.20,
+    max_extension=0.50, min_short_extension_cap=0.25, min_volume_ratio=1.75, min_range_position=0.75,
+    max_upper_wick=0.30, atr_stop_mult=2.2, min_stop_loss_pct=1.5, max_stop_loss_pct=2.0)
+_TG_INT_PARAMS = ("lookback_high", "volume_window", "min_history", "full_extension_bars")
+
+
+@device_entry
+def top_gainer_entry(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Tensor, v: torch.Tensor,
+                     qv: torch.Tensor | None = None, atr: torch.Tensor | None = None, *,
+                     risk_ok: torch.Tensor | None = None, first_t=None, lens=None, columns=_lib.TGE_VALUES,
+                     **thresholds):
+    """TopGainerEarlyMomentum's features, breakout gate and two-close
+    confirmation at every candle, one pass (strategies/top_gainer_early_momentum.py
+    :91-253, :363-406; bq_top_gainer_entry): column t of row s = the
+    reference on df.iloc[first_t[s]:t + 1]. Panels [S, T] float64 with unit
+    stride along T and any row pitch; qv None: the reference's volume * close
+    fall-backs; atr None: 0.0; risk_ok [S, T] bool (_risk_profile_allows per
+    candle; None: allowed). Returns (status uint8, entry uint8, score,
+    stop_loss_pct, values): status / entry are _lib.TGE_REASONS codes
+    (TGE_NO_FRAME where t >= lens[s]); values maps each name of `columns` (a
+    subset of _lib.TGE_VALUES; others are not written) to [S, T] float64,
+    NaN where the feature status is not ready; score / stop_loss_pct [S, T]
+    are UNROUNDED — the reference's round_numbers(.., 4) is the host's step —
+    and NaN except where status is 0 or risk_rejected. thresholds:
+    TOP_GAINER_DEFAULTS' keys."""
+    bad = set(thresholds) - set(TOP_GAINER_DEFAULTS)
+    if bad:
+        raise ValueError(f"top_gainer_entry: unknown thresholds {sorted(bad)} (known: {sorted(TOP_GAINER_DEFAULTS)})")
+    par = {**TOP_GAINER_DEFAULTS, **thresholds}
+    if int(par["min_history"]) < 25:
+        raise ValueError("top_gainer_entry: min_history must be >= 25 (the returns reach t - 24)")
+    for k in ("lookback_high", "volume_window", "full_extension_bars"):
+        if not 1 <= int(par[k]) <= _lib.TGE_MAX_LOOKBACK:
+            raise ValueError(f"top_gainer_entry: {k} must be in 1..{_lib.TGE_MAX_LOOKBACK}, got {par[k]}")
+    columns = tuple(columns)
+    unknown = [k for k in columns if k not in _lib.TGE_VALUES]
+    if unknown:
+        raise ValueError(f"top_gainer_entry: unknown columns {unknown}")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    named = [(o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume")]
+    named += [(x, n) for x, n in ((qv, "quote_volume"), (atr, "atr")) if x is not None]
+    for x, name in named:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    if risk_ok is not None and (not isinstance(risk_ok, torch.Tensor) or risk_ok.dtype != torch.bool
+                                or tuple(risk_ok.shape) != (S, T)):
+        raise ValueError(f"risk_ok: expected a bool tensor of shape {(S, T)}")
+    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in named[:5]])
+    qv = _check_panel(qv, "quote_volume") if qv is not None else None
+    atr = _check_panel(atr, "atr") if atr is not None else None
+    if risk_ok is not None:
+        if not risk_ok.is_cuda:
+            raise ValueError("risk_ok: expected a CUDA tensor (no CPU path)")
+        if T > 1 and risk_ok.stride(1) != 1:
+            risk_ok = risk_ok.contiguous()
+    dev = c.device
+    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
+    p = _lib.BqTopGainerParams()
+    for k, val in par.items():
+        setattr(p, k, int(val) if k in _TG_INT_PARAMS else float(val))
+    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    entry = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    sc = torch.empty((S, T), dtype=torch.float64, device=dev)
+    sl = torch.empty((S, T), dtype=torch.float64, device=dev)
+    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
+    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.TGE_VALUES])
+    st = _lib.load().bq_top_gainer_entry(
+        _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), ld_in, _ptr(qv),
+        _row_stride(qv) if qv is not None else T, _ptr(atr), _row_stride(atr) if atr is not None else T,
+        _ptr(risk_ok), _row_stride(risk_ok) if risk_ok is not None else T, _ptr(lens), _ptr(first_t), S, T,
+        ctypes.byref(p), _ptr(status), _ptr(entry), _ptr(sc), _ptr(sl), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_top_gainer_entry")
+    return status, entry, sc, sl, outs
+
+
 RETEST_DEFAULTS = dict(   # GradualGainerRetest's class attributes (:78-85)
     watch_ms=8 * 3_600_000, min_history=100, breakout_lookback=8, support_factor=1 - 0.5 / 100,
     pullback_factor=1 - 0.04)

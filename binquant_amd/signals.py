@@ -26,6 +26,11 @@ prefix frame df.iloc[:t + 1]:
                      (strategies/gradual_gainer_retest.py:222-308): the watchlist
                      state machine replayed per row (bq_retest.hip), with
                      retest_risk_allows for _risk_allows (:198-215)
+* top_gainer_entry   TopGainerEarlyMomentum's _features, _entry_allows and
+                     signal()'s two-close confirmation
+                     (strategies/top_gainer_early_momentum.py:91-253, :363-406),
+                     one pass (bq_topgainer.hip), with top_gainer_risk_allows
+                     for _risk_profile_allows (:204-234)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -402,6 +407,97 @@ def impulse_rider_features(o, h, l, c, atr, open_time, btc_time, btc_close, *, f
     (1 - RETEST_DISCOUNT_PCT / 100, formed in Python floats)."""
     return engine.impulse_rider(o, h, l, c, atr, open_time, btc_time, btc_close, first_t=first_t, lens=lens,
                                 columns=columns, check_bench=check_bench, **thresholds)
+
+
+# TopGainerEarlyMomentum's decisions, as uint8 codes (bq_top_gainer_entry's
+# BQ_TGE_*): the feature status, the first failing check of _entry_allows, the
+# two confirmation rules and the risk branch. Code 0 reads
+# top_gainer_breakout_ignition in the `entry` column (TGE_ENTRY_REASONS) and
+# top_gainer_breakout_two_close_confirmation in `status` (TGE_REASONS).
+(TGE_CONFIRMED, TGE_SHORT_HISTORY, TGE_INVALID_CANDLE, TGE_NOT_READY, TGE_NOT_BREAKING, TGE_NOT_ABOVE_EMAS,
+ TGE_NOT_GREEN, TGE_CANDLE_EXTENDED, TGE_HOUR_EXTENDED, TGE_EXTENSION, TGE_NOT_ACCELERATING, TGE_SIX_HOUR,
+ TGE_VOLUME_LOW, TGE_NOT_NEAR_HIGH, TGE_UPPER_WICK, TGE_FIRST_CONFIRM, TGE_SECOND_CONFIRM,
+ TGE_RISK_REJECTED) = range(18)
+TGE_NO_FRAME = _lib.TGE_NO_FRAME   # t >= lens[s]: no such message (not a reference reason)
+TGE_REASONS = dict(enumerate(_lib.TGE_REASONS))
+TGE_ENTRY_REASONS = {**{k: v for k, v in TGE_REASONS.items() if k < TGE_FIRST_CONFIRM},
+                     TGE_CONFIRMED: _lib.TGE_ENTRY_OK}
+TGE_KEYS = _lib.TGE_VALUES
+
+
+def top_gainer_entry(o, h, l, c, v, qv=None, atr=None, *, risk_ok=None, first_t=None, lens=None, columns=TGE_KEYS,
+                     **thresholds):
+    """TopGainerEarlyMomentum.signal() up to the message (strategies/
+    top_gainer_early_momentum.py:363-406) for every candle of the panel, with
+    its _features (:91-159) and _entry_allows (:161-188), in one pass
+    (engine.top_gainer_entry, bq_top_gainer_entry). Column t of row s = the
+    reference on the frame df.iloc[first_t[s]:t + 1] (first_t: the rows
+    Candles.post_process dropped, default 0). qv: the quote_asset_volume
+    column (None: the reference's volume * close fall-backs); atr: the frame's
+    ATR column (None: 0.0); risk_ok [S, T] bool: _risk_profile_allows per
+    candle (top_gainer_risk_allows; None: allowed).
+
+    Returns {"status": uint8 [S, T], signal()'s outcome for the message whose
+    newest candle is t (TGE_* codes, TGE_REASONS their strings; 0 =
+    top_gainer_breakout_two_close_confirmation, TGE_NO_FRAME where
+    t >= lens[s]); "entry": uint8 [S, T], the feature status or the first
+    failing check of _entry_allows on the prefix frame ending at t
+    (TGE_ENTRY_REASONS; 0 = top_gainer_breakout_ignition); "score" /
+    "stop_loss_pct": [S, T] float64, _score of the breakout candle t - 2 and
+    _stop_loss_pct(close[t], atr[t]) where status is 0 or TGE_RISK_REJECTED,
+    NaN elsewhere — both UNROUNDED: the reference's round_numbers(.., 4) is
+    pybinbot's and stays a host step; "values": {key: [S, T] float64} for
+    `columns` (a subset of TGE_KEYS), the prefix frame's value where the
+    feature status is ready, NaN elsewhere (top_gainer_features' convention)}.
+    The point-wise values are the reference's bits; ema20 / ema50 and the two
+    volume ratios agree with pandas to rounding. _already_emitted compares
+    open times for equality only and stays with the host. thresholds:
+    engine.TOP_GAINER_DEFAULTS' keys."""
+    status, entry, score, stop, values = engine.top_gainer_entry(o, h, l, c, v, qv, atr, risk_ok=risk_ok,
+                                                                 first_t=first_t, lens=lens, columns=columns,
+                                                                 **thresholds)
+    return {"status": status, "entry": entry, "score": score, "stop_loss_pct": stop, "values": values}
+
+
+# TopGainerEarlyMomentum._risk_profile_allows' reasons (:204-234), as uint8 codes: the first failing check in the
+# method's order
+TG_RISK_REASONS = ("risk_profile_allows_long", "market_context_unavailable", "market_stress_too_high",
+                   "market_context_short_edge", "btc_context_down", "symbol_regime_unavailable",
+                   "relative_strength_vs_btc_not_positive", "symbol_atr_too_high", "symbol_transition_not_long",
+                   "symbol_trend_down")
+
+
+def top_gainer_risk_allows(market_stress_score, long_regime_score, short_regime_score, btc_regime_score, btc_return,
+                           context_ok, relative_strength_vs_btc, atr_pct, micro_regime, micro_transition,
+                           trend_score, features_ok, max_market_stress: float = 0.25,
+                           min_relative_strength: float = 0.03, max_atr_pct: float = 0.06):
+    """TopGainerEarlyMomentum._risk_profile_allows (strategies/top_gainer_early_momentum.py
+    :204-234) per (symbol, candle): the context's market_stress_score /
+    long_regime_score / short_regime_score / btc_regime_score / btc_return [T]
+    float64 and context_ok [T] bool (False: no context), the symbol features
+    relative_strength_vs_btc / atr_pct / trend_score [S, T] float64,
+    micro_regime / micro_transition [S, T] int8 (_lib.MICRO_REGIMES /
+    MICRO_TRANSITIONS codes, negative: none) and features_ok [S, T] bool
+    (False: the context has no features for the symbol). Returns (ok bool
+    [S, T], reason uint8 [S, T]): the first failing check in the method's
+    order, TG_RISK_REASONS its strings (0 = risk_profile_allows_long). One
+    fused element-wise program."""
+    S, T = atr_pct.shape
+    down = float(_lib.MICRO_REGIMES.index("TREND_DOWN"))
+    blocked = [float(_lib.MICRO_TRANSITIONS.index(k)) for k in ("BREAKDOWN", "ENTERED_TREND_DOWN",
+                                                                "VOLATILITY_EXPANSION")]
+    STRESS, LONG, SHORT = F.inp(market_stress_score), F.inp(long_regime_score), F.inp(short_regime_score)
+    REG, RET = F.inp(btc_regime_score), F.inp(btc_return)
+    RS, ATR, TREND = F.inp(relative_strength_vs_btc), F.inp(atr_pct), F.inp(trend_score)
+    MR, MT = F.inp(micro_regime.to(torch.float64)), F.inp(micro_transition.to(torch.float64))
+    checks = [~F.inp(context_ok), STRESS >= max_market_stress, SHORT > LONG + 0.15, (REG < -0.2) & (RET < 0.0),
+              ~F.inp(features_ok), RS <= min_relative_strength, ATR > max_atr_pct,
+              (MT == blocked[0]) | (MT == blocked[1]) | (MT == blocked[2]), (MR == down) & (TREND < 0.0)]
+    code = F.const(0.0)
+    for i in range(len(checks), 0, -1):
+        code = F.where(checks[i - 1], float(i), code)
+    reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
+    return reason == 0, reason
 
 
 def bb_width_stable(bb_upper, bb_mid, bb_lower, n: int = 8, max_change_pct: float = 20.0, *, first_t=None,

@@ -51,6 +51,9 @@
  *                         (strategies/grid/ladder_deployer.py:42-56)
  *   bq_retest_replay   <- GradualGainerRetest.signal()'s watchlist state machine
  *                         (strategies/gradual_gainer_retest.py:222-308)
+ *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
+ *                         signal()'s two-close confirmation
+ *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
  *   bq_breadth_partial <- the per-symbol sums/counts of
  *                         LiveMarketContextAccumulator._build_context
  *                         market_regime/live_market_context_accumulator.py:135-163
@@ -456,6 +459,114 @@ int bq_impulse_rider(const double* open, const double* high, const double* low, 
 int bq_bb_stable(const double* bb_upper, const double* bb_mid, const double* bb_lower, int64_t ld_in,
                  const int64_t* lens, const int64_t* first_t, int64_t S, int64_t T, int32_t n,
                  double max_change_pct, uint8_t* stable, double* change_pct, int64_t ld_out, void* stream);
+
+/*
+ * TopGainerEarlyMomentum at every candle of the panel, one pass over the row
+ * (strategies/top_gainer_early_momentum.py): the features of the prefix frame
+ * (_features, :91-159), the breakout gate (_entry_allows, :161-188) and
+ * signal()'s two-close confirmation (:190-202, :363-406). Column t of row s
+ * stands for the frame df.iloc[first:t + 1], first = first_t[s] (NULL: 0),
+ * t < lens[s] (NULL: T). open / high / low / close / volume [S][ld_in];
+ * quote_volume [S][ld_qv] (NULL: the reference's fall-backs volume * close
+ * and volume_ma * close, :110-119); atr [S][ld_atr], the frame's ATR column
+ * (NULL: 0.0, :120); risk_ok [S][ld_risk] bytes, _risk_profile_allows per
+ * candle (:204-234; NULL: allowed).
+ *
+ * Features: previous_high = the NaN-skipping max of the lookback_high highs
+ * before t (:108); volume_ma / quote_volume_ma = rolling(volume_window).mean()
+ * with pandas' rules (min_periods = window, +-inf missing, the same-value
+ * rule; :109, :115-117); the returns over 4 / 8 / 24 candles (:141-143); the
+ * extension anchor close[first + max(0, t - first - full_extension_bars)]
+ * with its window and scaled cap (:124-132); ema20 / ema50 =
+ * close.ewm(span, adjust=False).mean() seeded at first (:153-154; a missing
+ * close decays the old weight as pandas does). The point-wise values are the
+ * reference's own expressions, bit for bit; the two ewm columns and the two
+ * volume ratios agree with pandas to rounding.
+ *
+ * entry [S][ld_out] bytes: the feature status (history_too_short :93,
+ * invalid_candle_values :105 — Python's min(): a NaN first argument sticks, a
+ * NaN elsewhere is skipped —, indicators_not_ready :157), else the first
+ * failing check of _entry_allows, else 0 (top_gainer_breakout_ignition).
+ * status [S][ld_out] bytes: signal()'s outcome for the message whose newest
+ * candle is t: history_too_short (t + 1 - first < min_history + 2, :364), else
+ * entry[t - 2] if non-zero (:369-377), else the two confirmation rules on
+ * close[t - 1] / close[t] (:198-201), else RISK_REJECTED where risk_ok[t] is
+ * 0 (:397-406), else 0 (top_gainer_breakout_two_close_confirmation). Both are
+ * BQ_TGE_NO_FRAME where t >= lens[s].
+ *
+ * values: BQ_TGE_NVALUES device pointers [S][ld_out] in _features' key order
+ * (:133-156; a NULL entry, or values == NULL, skips the column): the prefix
+ * frame's value where the feature status is ready, NaN elsewhere. score /
+ * stop_loss_pct [S][ld_out] (NULL = skip): _score of the breakout candle
+ * t - 2 (:246-253) and _stop_loss_pct(close[t], atr[t]) (:236-243, Python's
+ * min / max argument order for a NaN) where status is 0 or RISK_REJECTED, NaN
+ * elsewhere. Both are UNROUNDED: the reference rounds them with pybinbot's
+ * round_numbers(.., 4), which is not part of it; rounding is the host's step.
+ *
+ * Not built: _already_emitted (:255-258, :410-413) compares candle open times
+ * for equality only, so it cannot fire between distinct candles of a panel;
+ * it stays with the host, as do the market-type check and the message.
+ *
+ * params NULL: the class attributes (bq_top_gainer_default_params). BQ_EINVAL
+ * for a NULL required pointer (the five inputs, status, entry), a pitch < T,
+ * lookback_high / volume_window / full_extension_bars outside
+ * 1..BQ_TGE_MAX_LOOKBACK (the ring's halo), min_history < 25 (the returns
+ * reach t - 24), S or T beyond 2^31. S == 0 or T == 0: BQ_OK, no launch. No
+ * workspace, nothing allocated.
+ */
+#define BQ_TGE_MAX_LOOKBACK 96
+#define BQ_TGE_CONFIRMED          0   /* entry: top_gainer_breakout_ignition (:188); status: ..._two_close_confirmation (:202) */
+#define BQ_TGE_SHORT_HISTORY      1   /* history_too_short (:94, :365) */
+#define BQ_TGE_INVALID_CANDLE     2   /* invalid_candle_values (:106) */
+#define BQ_TGE_NOT_READY          3   /* indicators_not_ready (:158) */
+#define BQ_TGE_NOT_BREAKING       4   /* not_breaking_recent_high (:164) */
+#define BQ_TGE_NOT_ABOVE_EMAS     5   /* not_above_ema20_and_ema50 (:166) */
+#define BQ_TGE_NOT_GREEN          6   /* candle_not_green_enough (:168) */
+#define BQ_TGE_CANDLE_EXTENDED    7   /* single_candle_too_extended (:170) */
+#define BQ_TGE_HOUR_EXTENDED      8   /* one_hour_move_too_extended (:172) */
+#define BQ_TGE_EXTENSION          9   /* extension_move_too_extended (:174) */
+#define BQ_TGE_NOT_ACCELERATING  10   /* momentum_not_accelerating (:179) */
+#define BQ_TGE_SIX_HOUR          11   /* six_hour_move_not_confirmed (:181) */
+#define BQ_TGE_VOLUME_LOW        12   /* volume_ratio_too_low (:183) */
+#define BQ_TGE_NOT_NEAR_HIGH     13   /* close_not_near_high (:185) */
+#define BQ_TGE_UPPER_WICK        14   /* upper_wick_too_large (:187) */
+#define BQ_TGE_FIRST_CONFIRM     15   /* first_confirmation_did_not_hold_breakout (:199) */
+#define BQ_TGE_SECOND_CONFIRM    16   /* second_confirmation_did_not_clear_breakout_close (:201) */
+#define BQ_TGE_RISK_REJECTED     17   /* _risk_profile_allows refused (:397-406) */
+#define BQ_TGE_NO_FRAME         255   /* t >= lens[s]: no such message */
+/* value columns, _features' key order (:133-156): close, open, high, low,
+ * volume, quote_volume, previous_high, return_1h, return_2h, return_6h,
+ * extension_return, extension_window_bars, extension_cap, candle_return,
+ * volume_ratio, quote_volume_ratio, range_position, upper_wick_fraction,
+ * ema20, ema50, atr */
+#define BQ_TGE_NVALUES 21
+typedef struct bq_top_gainer_params {
+  int32_t lookback_high;          /* LOOKBACK_HIGH_WINDOW 48 */
+  int32_t volume_window;          /* VOLUME_WINDOW 32 */
+  int32_t min_history;            /* MIN_HISTORY 56 (>= 25) */
+  int32_t full_extension_bars;    /* FULL_EXTENSION_WINDOW_BARS 96 */
+  double min_candle_return;       /* MIN_CANDLE_RETURN 0.01 */
+  double max_candle_return;       /* MAX_CANDLE_RETURN 0.10 */
+  double min_return_1h;           /* MIN_RETURN_1H 0.05 */
+  double min_return_2h;           /* MIN_RETURN_2H 0.08 */
+  double min_return_6h;           /* MIN_RETURN_6H 0.07 */
+  double max_return_1h;           /* MAX_RETURN_1H 0.20 */
+  double max_extension;           /* MAX_EXTENSION_RETURN 0.50 */
+  double min_short_extension_cap; /* MIN_SHORT_HISTORY_EXTENSION_CAP 0.25 */
+  double min_volume_ratio;        /* MIN_VOLUME_RATIO 1.75 */
+  double min_range_position;      /* MIN_CLOSE_RANGE_POSITION 0.75 */
+  double max_upper_wick;          /* MAX_UPPER_WICK_FRACTION 0.30 */
+  double atr_stop_mult;           /* ATR_STOP_MULT 2.2 (:64) */
+  double min_stop_loss_pct;       /* MIN_STOP_LOSS_PCT 1.5 (:65) */
+  double max_stop_loss_pct;       /* MAX_STOP_LOSS_PCT 2.0 (:66) */
+} bq_top_gainer_params;
+void bq_top_gainer_default_params(bq_top_gainer_params* p);
+int bq_top_gainer_entry(const double* open, const double* high, const double* low, const double* close,
+                        const double* volume, int64_t ld_in, const double* quote_volume, int64_t ld_qv,
+                        const double* atr, int64_t ld_atr, const uint8_t* risk_ok, int64_t ld_risk,
+                        const int64_t* lens, const int64_t* first_t, int64_t S, int64_t T,
+                        const bq_top_gainer_params* params, uint8_t* status, uint8_t* entry, double* score,
+                        double* stop_loss_pct, double* const* values, int64_t ld_out, void* stream);
 
 /* ---- benchmark-relative statistics ---------------------------------------- */
 /*

@@ -1,6 +1,6 @@
 """Per-§8-row device timings (diagnostic, GPU): each strategy pipeline and
 generic kernel at S symbols x T candles, HIP-event timed on the launch stream.
-Usage: python tools/row_costs.py [S] [T]"""
+Usage: python tools/row_costs.py [S] [T] [row ...]   (no row names: every row)"""
 import json
 import os
 import sys
@@ -54,14 +54,19 @@ rows = {
     "adx": lambda: signals.adx(h, l, c),
     "zscore": lambda: signals.zscore(c),
     "top_gainer": lambda: signals.top_gainer_features(o, h, l, c, v, qv),
+    # the same inputs in one pass: the 21 values plus entry / status / score / stop_loss_pct
+    "top_gainer_entry": lambda: signals.top_gainer_entry(o, h, l, c, v, qv),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
     "align": lambda: engine.align(ts, ts[0], btc),
     "join_returns": lambda: engine.join_returns(ts, c, ts[0], btc, capacity=T),
 }
+only = sys.argv[3:]
 res = {}
 for name, fn in rows.items():
+    if only and name not in only:
+        continue
     try:
         ms = timeit(fn)
         res[name] = {"ms": round(ms, 4), "Gcandles_s": round(S * T / ms / 1e6, 2)}
