@@ -210,6 +210,20 @@ BQ_RT_D_SUPPORT, BQ_RT_D_PULLBACK, BQ_RT_D_RECLAIM, BQ_RT_D_EXPIRED = 1, 2, 4, 8
 RT_EVENTS = ("idle", "watch_set", "watching", "risk_blocked", "candidate", "history_too_short")
 
 
+class BqSpikeFadeParams(ctypes.Structure):
+    """Mirror of ``bq_spike_fade_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("window_bars", ctypes.c_int32), ("ext_factor", ctypes.c_double)]
+
+
+# bq_spike_fade_replay: event codes (BQ_FS_*), detail bits (BQ_FS_D_*)
+SPIKEFADE_MAX_WINDOW = 32
+(BQ_FS_IDLE, BQ_FS_SOURCE_SET, BQ_FS_WAITING, BQ_FS_CANDIDATE, BQ_FS_CLEARED, BQ_FS_SAME_CANDLE) = range(6)
+BQ_FS_NO_FRAME = 255
+(BQ_FS_D_SOURCE, BQ_FS_D_MARKET, BQ_FS_D_NEW_HIGH, BQ_FS_D_CANDLE_EXPIRED, BQ_FS_D_WINDOW_EXPIRED,
+ BQ_FS_D_EXTENSION) = 1, 2, 4, 8, 16, 32
+FS_EVENTS = ("idle", "source_set", "waiting", "candidate", "cleared", "same_candle")
+
 
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
@@ -291,6 +305,9 @@ SIGNATURES: dict[str, tuple] = {
     "bq_retest_default_params": (None, [ctypes.POINTER(BqRetestParams)]),
     "bq_retest_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                         ctypes.POINTER(BqRetestParams), _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "bq_spike_fade_default_params": (None, [ctypes.POINTER(BqSpikeFadeParams)]),
+    "bq_spike_fade_replay": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                            ctypes.POINTER(BqSpikeFadeParams), _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

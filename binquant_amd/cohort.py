@@ -21,7 +21,8 @@ all S symbols of the cohort in one call:
   (live_market_context_accumulator.py:95-297, bq_context_partials);
 * the 15m strategies' feature pipelines: LiquidationSweepPump,
   FailedSpikeFade, TopGainerEarlyMomentum, GradualGainerRetest's leadership
-  (:445-499).
+  (:445-499), and on request the decision bodies built on them (gates,
+  retest, top_entry, spike_fade below).
 
 Nothing reads back to the host, so the whole cohort can be captured once
 as a hipGraph (``graphs.CapturedPipeline(process_cohort, ...)``) and
@@ -67,7 +68,8 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                    max_bars: int = 400, exact: bool = True, h1_max_bins: int | None = None,
                    gates: bool = False, retest: signals.RetestState | None = None,
                    retest_risk: torch.Tensor | None = None, top_entry: bool = False,
-                   top_risk: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+                   top_risk: torch.Tensor | None = None, spike_fade: signals.SpikeFadeState | None = None,
+                   spike_fade_market: tuple | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -96,8 +98,19 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     topentry.status / topentry.entry (uint8 [S, T15]) and topentry.score /
     topentry.stop_loss_pct (unrounded). top_risk: _risk_profile_allows per
     candle, bool [S, T15] (or [S]; None: allowed). The default leaves the
-    returned dict and the launch sequence as they were. Returns a flat dict of
-    tensors (names prefixed by the stage)."""
+    returned dict and the launch sequence as they were. spike_fade: the
+    cohort's FailedSpikeFade pending spikes (signals.SpikeFadeState, [S]): the
+    body of its signal() (:596-695 of the strategy) runs on the newest 15m
+    candle, after the spike stage and on its stream — source_spike_allows
+    formed from spike.* (the newest column is the frame-ending-here value) —
+    from that state, which is updated in place (a captured graph carries it
+    from message to message); spikefade.event / spikefade.detail /
+    spikefade.bars [S] are added. spike_fade_market: (source_ok, failure_ok)
+    of signals.spike_fade_market_allows for that candle, each bool [T15] or
+    one element (broadcast; both [S, T15] where the rows see different
+    contexts), or None (allowed). Without a state the outputs
+    and launches are unchanged. Returns a flat dict of tensors (names
+    prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -152,6 +165,17 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     def spike(out):
         for k, v in strategies.failed_spike_features(o15, h15, l15, c15, v15, v15 * c15, exact=exact).items():
             out[f"spike.{k}"] = v
+        if spike_fade is not None:   # signal()'s body on the cohort's message: the newest candle only
+            ok, _ = signals.spike_source_allows(*(out[f"spike.{k}"] for k in (
+                "label", "price_break_flag", "cumulative_price_break_flag", "accel_spike_flag", "close_open_ratio",
+                "upward")))
+            src_m, fail_m = (None if m is None else m if m.dim() == 2 else m.reshape(-1).expand(T15)
+                             for m in (spike_fade_market or (None, None)))
+            newest = torch.full((S,), T15 - 1, dtype=torch.int64, device=c15.device)
+            fs = signals.failed_spike_fade(o15, h15, c15, ts15, ok, src_market=src_m, fail_market=fail_m,
+                                           state=spike_fade, from_t=newest)
+            for k in ("event", "detail", "bars"):
+                out[f"spikefade.{k}"] = fs[k][:, -1]
 
     def top(out):
         feats, status = signals.top_gainer_features(o15, h15, l15, c15, v15, v15 * c15)

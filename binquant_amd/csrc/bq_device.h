@@ -119,6 +119,18 @@ __device__ __forceinline__ double readlane_f64(double x, int lane) {
   return __hiloint2double(hi, lo);
 }
 
+__device__ __forceinline__ int64_t readlane_i64(int64_t x, int lane) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(x & 0xffffffffll), lane);
+  const int hi = __builtin_amdgcn_readlane((int)(x >> 32), lane);
+  return ((int64_t)hi << 32) | (int64_t)lo;
+}
+
+// a per-row int64 (lens / first_t / from_t of the replay kernels; NULL: dflt), clamped to [0, T]
+__device__ __forceinline__ int clamp_row(const int64_t* v, int64_t s, int64_t dflt, int T) {
+  const int64_t x = v ? v[s] : dflt;
+  return x < 0 ? 0 : x > T ? T : (int)x;
+}
+
 // Inclusive wave prefix of a double-double: DPP row scans, then the row totals
 // (lanes 15, 31, 47) folded in through readlane.
 __device__ __forceinline__ dd wave_scan_dd_dpp(dd x, int lane) {

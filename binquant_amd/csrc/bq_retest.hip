@@ -59,17 +59,6 @@ struct RetestStep {
   uint8_t lead, risk;
 };
 
-__device__ __forceinline__ int64_t readlane_i64(int64_t x, int lane) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(x & 0xffffffffll), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(x >> 32), lane);
-  return ((int64_t)hi << 32) | (int64_t)lo;
-}
-
-__device__ __forceinline__ int clamp_row(const int64_t* v, int64_t s, int64_t dflt, int T) {
-  const int64_t x = v ? v[s] : dflt;
-  return x < 0 ? 0 : x > T ? T : (int)x;
-}
-
 __global__ __launch_bounds__(RT_NT) void retest_kernel(const RetestArgs A) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int64_t s = (int64_t)blockIdx.x * RT_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);

@@ -11,6 +11,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import functools
+import math
 from dataclasses import dataclass, field
 
 import torch
@@ -1678,6 +1679,100 @@ def retest_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Te
                                       _ptr(ss), _ptr(sl), _ptr(event), _ptr(det), _ptr(lvl), T, _stream_handle(None))
     _lib.check(st, "bq_retest_replay")
     return event, det, lvl
+
+
+SPIKE_FADE_DEFAULTS = dict(   # FailedSpikeFade's class attributes (:42-43)
+    window_bars=8, ext_factor=1 + 0.06)
+
+
+@device_entry
+def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_time: torch.Tensor,
+                      source_ok: torch.Tensor, src_market: torch.Tensor | None = None,
+                      fail_market: torch.Tensor | None = None, *, state=None, first_t=None, lens=None, from_t=None,
+                      detail: bool = True, bars: bool = True, **params):
+    """FailedSpikeFade.signal()'s pending-spike state machine replayed over
+    the panel (strategies/failed_spike_fade.py:596-695; bq_spike_fade_replay):
+    column t of row s = the method on the message whose frame is
+    df.iloc[first_t[s]:t + 1], after the messages of all earlier candles;
+    candles max(from_t[s], first_t[s]) .. lens[s] - 1 are replayed. Panels
+    [S, T] float64 with unit stride along T and any row pitch, open_time
+    [S, T] int64 ms, strictly ascending within a row's frame; source_ok [S, T]
+    bool: source_spike_allows of the frame ending at t. src_market /
+    fail_market: source_market_allows / failure_market_allows per candle,
+    bool [S, T] or [T] (one row shared by all symbols; None: always allowed).
+    state: None (start idle, discard) or the (active uint8, open_time int64,
+    high float64, close float64) [S] tensors, updated in place. Returns
+    (event uint8, detail uint8 or None, bars uint8 or None), each [S, T]
+    (_lib.BQ_FS_*). params: SPIKE_FADE_DEFAULTS' keys (ext_factor formed in
+    Python floats)."""
+    bad = set(params) - set(SPIKE_FADE_DEFAULTS)
+    if bad:
+        raise ValueError(f"spike_fade_replay: unknown parameters {sorted(bad)} (known: {sorted(SPIKE_FADE_DEFAULTS)})")
+    par = {**SPIKE_FADE_DEFAULTS, **params}
+    W, ef = int(par["window_bars"]), float(par["ext_factor"])
+    if not 1 <= W <= _lib.SPIKEFADE_MAX_WINDOW:
+        raise ValueError(f"spike_fade_replay: window_bars must be in 1..{_lib.SPIKEFADE_MAX_WINDOW}, got {W}")
+    if not math.isfinite(ef):
+        raise ValueError(f"spike_fade_replay: ext_factor must be finite, got {ef}")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    for x, name in ((o, "open"), (h, "high"), (c, "close")):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
+        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
+    if not isinstance(source_ok, torch.Tensor) or source_ok.dtype != torch.bool or tuple(source_ok.shape) != (S, T):
+        raise ValueError(f"source_ok: expected a bool tensor of shape {(S, T)}")
+    for m, name in ((src_market, "src_market"), (fail_market, "fail_market")):
+        if m is not None and (not isinstance(m, torch.Tensor) or m.dtype != torch.bool
+                              or tuple(m.shape) not in ((S, T), (T,))):
+            raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)} or {(T,)}")
+    shared = [m.dim() == 1 for m in (src_market, fail_market) if m is not None]
+    if len(set(shared)) > 1:
+        raise ValueError("src_market / fail_market: both [S, T] or both [T] (they share one row stride)")
+    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
+        _gate_rows(from_t, "from_t", S)
+    if state is not None:
+        if len(state) != 4:
+            raise ValueError("state: expected (active, open_time, high, close)")
+        for x, name, dt in zip(state, ("state.active", "state.open_time", "state.high", "state.close"),
+                               (torch.uint8, torch.int64, torch.float64, torch.float64)):
+            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in ((o, "open"), (h, "high"), (c, "close"))])
+    ts = _check_ts(open_time, "open_time")
+    masks = [m for m in (src_market, fail_market) if m is not None]
+    if not all(x.is_cuda for x in [source_ok] + masks + list(state or ())):
+        raise ValueError("source_ok / src_market / fail_market / state: expected CUDA tensors (no CPU path)")
+    if T > 1 and source_ok.stride(1) != 1:
+        source_ok = source_ok.contiguous()
+    ld_m = T
+    if masks and shared[0]:
+        masks, ld_m = [m.contiguous() for m in masks], 0
+    elif masks:
+        if any(m.shape[1] > 1 and m.stride(1) != 1 for m in masks):
+            masks = [m.contiguous() for m in masks]
+        masks, ld_m = _common_pitch(masks)
+    masks = iter(masks)
+    sm = next(masks) if src_market is not None else None
+    fm = next(masks) if fail_market is not None else None
+    dev = c.device
+    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    p = _lib.BqSpikeFadeParams(W, ef)
+    event = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    det = torch.empty((S, T), dtype=torch.uint8, device=dev) if detail else None
+    brs = torch.empty((S, T), dtype=torch.uint8, device=dev) if bars else None
+    sa, so, sh, sc = state if state is not None else (None, None, None, None)
+    st = _lib.load().bq_spike_fade_replay(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ld_in, _ptr(ts), T,
+                                          _ptr(source_ok), _row_stride(source_ok), _ptr(sm), _ptr(fm), ld_m,
+                                          _ptr(lens), _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(sa),
+                                          _ptr(so), _ptr(sh), _ptr(sc), _ptr(event), _ptr(det), _ptr(brs), T,
+                                          _stream_handle(None))
+    _lib.check(st, "bq_spike_fade_replay")
+    return event, det, brs
 
 
 def _join_capacity(ts: torch.Tensor, lens: torch.Tensor | None, bts: torch.Tensor) -> int:

@@ -31,6 +31,11 @@ prefix frame df.iloc[:t + 1]:
                      (strategies/top_gainer_early_momentum.py:91-253, :363-406),
                      one pass (bq_topgainer.hip), with top_gainer_risk_allows
                      for _risk_profile_allows (:204-234)
+* failed_spike_fade  the body of FailedSpikeFade.signal()
+                     (strategies/failed_spike_fade.py:596-695): the pending-spike
+                     state machine replayed per row (bq_spikefade.hip), with
+                     spike_source_allows (:190-203) and
+                     spike_fade_market_allows (:155-188)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -356,6 +361,127 @@ def retest_risk_allows(market_stress_score, btc_regime_score, btc_return, contex
         code = F.where(checks[i - 1], float(i), code)
     reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
     return reason == 0, reason
+
+
+# FailedSpikeFade.signal()'s per-candle outcome, as uint8 codes
+# (bq_spike_fade_replay's BQ_FS_*), and the detail bits beside them
+(FS_IDLE, FS_SOURCE_SET, FS_WAITING, FS_CANDIDATE, FS_CLEARED, FS_SAME_CANDLE) = range(6)
+FS_NO_FRAME = _lib.BQ_FS_NO_FRAME   # t < max(from_t[s], first_t[s]) or t >= lens[s]: no message replayed
+FS_EVENTS = dict(enumerate(_lib.FS_EVENTS))
+(FS_D_SOURCE, FS_D_MARKET, FS_D_NEW_HIGH, FS_D_CANDLE_EXPIRED, FS_D_WINDOW_EXPIRED, FS_D_EXTENSION) = (
+    _lib.BQ_FS_D_SOURCE, _lib.BQ_FS_D_MARKET, _lib.BQ_FS_D_NEW_HIGH, _lib.BQ_FS_D_CANDLE_EXPIRED,
+    _lib.BQ_FS_D_WINDOW_EXPIRED, _lib.BQ_FS_D_EXTENSION)
+
+
+class SpikeFadeState:
+    """The pending spikes of FailedSpikeFade for S rows (its strategy_states
+    entries): active uint8, and the source candle's open_time int64 (ms), high
+    and close float64, each [S] on the device (the entry's volume and
+    quote_asset_volume only feed the message text: gather them at t - bars).
+    signals.failed_spike_fade / engine.spike_fade_replay update it in place,
+    so a captured graph carries it from one replay to the next."""
+
+    __slots__ = ("active", "open_time", "high", "close")
+
+    def __init__(self, active: torch.Tensor, open_time: torch.Tensor, high: torch.Tensor, close: torch.Tensor):
+        self.active, self.open_time, self.high, self.close = active, open_time, high, close
+
+    @classmethod
+    def idle(cls, S: int, device) -> "SpikeFadeState":
+        return cls(torch.zeros(S, dtype=torch.uint8, device=device), torch.zeros(S, dtype=torch.int64, device=device),
+                   torch.full((S,), NAN, dtype=torch.float64, device=device),
+                   torch.full((S,), NAN, dtype=torch.float64, device=device))
+
+    def tensors(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.active, self.open_time, self.high, self.close
+
+
+# FailedSpikeFade.source_spike_allows' strings (:190-203), as uint8 codes: 0 allows, then the first failing check
+SPIKE_SOURCE_REASONS = ("symbol_confirmed_upward_price_impulse", "symbol_price_impulse_missing",
+                        "symbol_spike_too_extended", "symbol_upward_spike_missing")
+# source_market_allows / failure_market_allows' strings (:155-188): 0 and 1 allow (the reference appends the
+# breadth series' key, "_market_breadth_ma" or "_market_breadth", to them), then the first failing check
+SPIKE_MARKET_REASONS = ("source_breadth_up", "failure_breadth_down", "market_context_unavailable",
+                        "market_stress_too_high", "market_context_not_long", "breadth_momentum_unavailable",
+                        "source_breadth_not_up", "failure_breadth_not_down")
+
+
+def _first_true(checks, none: float):
+    """The code beside the first true check (`none` when none is)."""
+    code = F.const(none)
+    for cond, value in reversed(checks):
+        code = F.where(cond, float(value), code)
+    return code
+
+
+def spike_source_allows(label, price_break_flag, cumulative_price_break_flag, accel_spike_flag, close_open_ratio,
+                        upward, max_candle_return: float = 0.06):
+    """FailedSpikeFade.source_spike_allows (strategies/failed_spike_fade.py:190-203)
+    per (symbol, candle) on failed_spike_features' columns: label, the three
+    price-impulse flags and upward bool [S, T], close_open_ratio float64
+    [S, T]. Returns (ok bool [S, T], reason uint8 [S, T]): the first failing
+    check in the method's order, SPIKE_SOURCE_REASONS its strings (0 = allowed).
+    A NaN close_open_ratio passes, as nan > x does. One fused element-wise
+    program."""
+    S, T = close_open_ratio.shape
+    impulse = F.inp(price_break_flag) | F.inp(cumulative_price_break_flag) | F.inp(accel_spike_flag)
+    code = _first_true([(~F.inp(label) | ~impulse, 1), (F.inp(close_open_ratio) > max_candle_return, 2),
+                        (~F.inp(upward), 3)], 0.0)
+    reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
+    return reason == 0, reason
+
+
+def spike_fade_market_allows(market_stress_score, long_regime_score, short_regime_score, context_ok, momentum_points,
+                             max_market_stress: float = 0.35, min_momentum: float = 0.5):
+    """FailedSpikeFade.source_market_allows / failure_market_allows
+    (strategies/failed_spike_fade.py:155-188) per candle: the context's
+    market_stress_score / long_regime_score / short_regime_score [T] float64,
+    context_ok [T] bool (False: no context) and momentum_points [T] float64,
+    the caller's _breadth_momentum_points (NaN: breadth_momentum_unavailable).
+    Returns (source_ok bool, source_reason uint8, failure_ok bool,
+    failure_reason uint8), each [T]; the reasons index SPIKE_MARKET_REASONS
+    (0 / 1: the source / the failure gate allows). One fused element-wise
+    program."""
+    T = momentum_points.numel()
+    STRESS, LONG, SHORT, MOM = (F.inp(x.reshape(-1)) for x in (market_stress_score, long_regime_score,
+                                                              short_regime_score, momentum_points))
+    head = [(~F.inp(context_ok.reshape(-1)), 2), (STRESS >= max_market_stress, 3)]
+    src = _first_true(head + [(LONG <= SHORT, 4), (F.isnan(MOM), 5), (~(MOM >= min_momentum), 6)], 0.0)
+    fail = _first_true(head + [(F.isnan(MOM), 5), (~(MOM <= -min_momentum), 7)], 1.0)
+    res = F.run({"src": src, "fail": fail}, 1, T)
+    src_reason, fail_reason = res["src"].reshape(-1).to(torch.uint8), res["fail"].reshape(-1).to(torch.uint8)
+    return src_reason == 0, src_reason, fail_reason == 1, fail_reason
+
+
+def failed_spike_fade(o, h, c, open_time, source_ok, *, src_market=None, fail_market=None,
+                      state: SpikeFadeState | None = None, first_t=None, lens=None, from_t=None, **params):
+    """The body of FailedSpikeFade.signal() (strategies/failed_spike_fade.py
+    :596-695) for every candle of the panel: the pending-spike replay
+    (engine.spike_fade_replay, bq_spike_fade_replay). Column t of row s = the
+    method on the message whose frame is df.iloc[first_t[s]:t + 1], after the
+    messages of all earlier candles; candles from_t[s] .. lens[s] - 1 are
+    replayed, from `state` (None: idle), which is updated in place. open_time
+    ascends strictly within a row's frame.
+
+    source_ok [S, T] bool: column t must hold source_spike_allows of the
+    FRAME ENDING AT t (spike_source_allows on the newest column of
+    strategies.failed_spike_features of that frame). The cohort's newest
+    column is exactly that. A whole-row failed_spike_features over a long
+    panel is an approximation of it: detect()'s auto-calibration and cooldown
+    are frame-wide, so an earlier column of a long frame is not what the
+    message at that candle saw. The caller chooses. src_market / fail_market:
+    spike_fade_market_allows' source_ok / failure_ok, bool [T] or [S, T]
+    (None: allowed). params: engine.SPIKE_FADE_DEFAULTS' keys.
+
+    Returns {"event": uint8 [S, T] (FS_* codes, FS_EVENTS their names),
+    "detail": uint8 [S, T] (FS_D_* bits: the gate(s) that kept an idle candle
+    idle, the failed test(s) of a waiting candle, the reason a spike was
+    cleared), "bars": uint8 [S, T] (bars_elapsed at waiting / candidate /
+    cleared-by-window-or-extension candles, 0 elsewhere)}."""
+    event, detail, bars = engine.spike_fade_replay(o, h, c, open_time, source_ok, src_market, fail_market,
+                                                   state=state.tensors() if state is not None else None,
+                                                   first_t=first_t, lens=lens, from_t=from_t, **params)
+    return {"event": event, "detail": detail, "bars": bars}
 
 
 # RelativeStrengthImpulseRider._features reason strings, as uint8 codes

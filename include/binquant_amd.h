@@ -51,6 +51,8 @@
  *                         (strategies/grid/ladder_deployer.py:42-56)
  *   bq_retest_replay   <- GradualGainerRetest.signal()'s watchlist state machine
  *                         (strategies/gradual_gainer_retest.py:222-308)
+ *   bq_spike_fade_replay <- FailedSpikeFade.signal()'s pending-spike state machine
+ *                         (strategies/failed_spike_fade.py:596-695)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -381,6 +383,77 @@ int bq_retest_replay(const double* open, const double* high, const double* low, 
                      const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
                      const bq_retest_params* params, uint8_t* st_active, int64_t* st_started, double* st_level,
                      uint8_t* event, uint8_t* detail, double* level, int64_t ld_out, void* stream);
+
+/*
+ * FailedSpikeFade.signal()'s pending-spike state machine replayed over a panel
+ * (strategies/failed_spike_fade.py:596-695): column t of row s is what signal()
+ * does on the message whose frame is df.iloc[first:t + 1], first = first_t[s]
+ * (NULL: 0), after the messages of all earlier candles of the row. Candles
+ * t = max(from_t[s], first) (from_t NULL: 0) .. lens[s] - 1 (NULL: T) are
+ * replayed: a candle before first has an empty frame and no message.
+ * open / high / close [S][ld_in], open_time [S][ld_ts] int64 ms, source_ok
+ * [S][ld_b] 0 / 1 bytes: source_spike_allows (:190-203) of the frame ending at
+ * t. src_market / fail_market 0 / 1 bytes with row stride ld_m:
+ * source_market_allows / failure_market_allows (:155-188) at t; ld_m == 0: one
+ * [T] row shared by all symbols; either pointer NULL: always allowed.
+ *
+ * Per-row state: active and the pending spike's open_time, high, close (its
+ * volume and quote_asset_volume only feed the message text: the source candle
+ * is inside the frame, the caller gathers them at t - bars). Per candle, in
+ * the method's order (p: the last position in [first, t] whose open_time ==
+ * st_open_time; bars = t - p; post_high = max(high[p+1 .. t]), NaN skipped as
+ * pandas' max does, a NaN result fails the compare; failed_new_high = high[t]
+ * >= st_high and close[t] < open[t] and close[t] < st_close):
+ *   # condition                                     event, detail               state     lines
+ *   1 t outside [max(from_t, first), lens)          NO_FRAME (255)
+ *   2 idle, source_ok[t] and src_market[t]          SOURCE_SET                  st = (open_time[t], high[t],
+ *                                                                               close[t]) :618-630
+ *   3 idle, otherwise                               IDLE; D_SOURCE and / or     -         :638-646
+ *                                                   D_MARKET: the failed side(s)
+ *   4 pending, no p found                           CLEARED, D_CANDLE_EXPIRED   cleared   :648-655
+ *   5 pending, bars == 0                            SAME_CANDLE                 untouched :660-661
+ *   6 pending, bars > window_bars                   CLEARED, D_WINDOW_EXPIRED   cleared   :662-665
+ *   7 pending, post_high > st_high * ext_factor     CLEARED, D_EXTENSION        cleared   :667-677
+ *   8 pending, not (failed_new_high and             WAITING; D_NEW_HIGH         -         :679-693
+ *     fail_market[t])                               (failed_new_high false) and / or D_MARKET
+ *   9 pending, failed_new_high and fail_market[t]   CANDIDATE                   cleared   :695
+ * Rows 4, 6 and 7 return without looking for a new source on that candle: the
+ * candle is consumed (unlike the retest replay's expiry). Every test is a
+ * compare in the method's direction (a NaN fails it) and at most one correctly
+ * rounded fp64 multiply: events, details, bars and states are exact.
+ *
+ * Domain: open_time strictly ascending within [first, lens): p is unique.
+ * _fiat_order_size, the message text and the dispatch are the caller's.
+ *
+ * st_active / st_open_time / st_high / st_close [S]: read, then written in
+ * place with the state after the row's last replayed candle (0 / NaN where
+ * idle; a captured graph carries it); all four NULL: start idle, discard.
+ * event [S][ld_out] bytes (BQ_FS_*), detail [S][ld_out] bytes (BQ_FS_D_*, NULL
+ * = skip), bars [S][ld_out] bytes (NULL = skip): bars_elapsed at WAITING /
+ * CANDIDATE / CLEARED-by-window-or-extension candles (saturated at 255: only a
+ * carried-in spike can lie further back), 0 elsewhere. params NULL: the class
+ * attributes (bq_spike_fade_default_params). BQ_EINVAL unless 1 <= window_bars
+ * <= BQ_SPIKEFADE_MAX_WINDOW, ext_factor is finite, the state pointers are all
+ * NULL or all set, and every ld >= T (ld_m: or 0); checked before any launch.
+ * S == 0 or T == 0: BQ_OK. No workspace, nothing allocated.
+ */
+#define BQ_SPIKEFADE_MAX_WINDOW 32
+typedef struct bq_spike_fade_params {
+  int32_t window_bars;   /* FAILURE_WINDOW_BARS 8 */
+  double ext_factor;     /* 1 + MAX_POST_SPIKE_EXTENSION, formed by the caller in fp64 */
+} bq_spike_fade_params;
+enum { BQ_FS_IDLE = 0, BQ_FS_SOURCE_SET, BQ_FS_WAITING, BQ_FS_CANDIDATE, BQ_FS_CLEARED, BQ_FS_SAME_CANDLE,
+       BQ_FS_NO_FRAME = 255 };
+enum { BQ_FS_D_SOURCE = 1, BQ_FS_D_MARKET = 2, BQ_FS_D_NEW_HIGH = 4, BQ_FS_D_CANDLE_EXPIRED = 8,
+       BQ_FS_D_WINDOW_EXPIRED = 16, BQ_FS_D_EXTENSION = 32 };
+void bq_spike_fade_default_params(bq_spike_fade_params* p);
+int bq_spike_fade_replay(const double* open, const double* high, const double* close, int64_t ld_in,
+                         const int64_t* open_time, int64_t ld_ts, const uint8_t* source_ok, int64_t ld_b,
+                         const uint8_t* src_market, const uint8_t* fail_market, int64_t ld_m, const int64_t* lens,
+                         const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
+                         const bq_spike_fade_params* params, uint8_t* st_active, int64_t* st_open_time,
+                         double* st_high, double* st_close, uint8_t* event, uint8_t* detail, uint8_t* bars,
+                         int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t

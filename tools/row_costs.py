@@ -21,6 +21,7 @@ qv = v * c
 btc = c[0].clone()
 ts = (1_700_000_000_000 + 900_000 * torch.arange(T, device="cuda", dtype=torch.int64)).expand(S, T).contiguous()
 atr = engine.enrich(o, h, l, c, v, columns=("ATR",))["ATR"]
+spike_src = torch.rand(S, T, device="cuda") < 0.05   # a source_ok mask of the failed-spike-fade replay
 
 
 def timeit(fn, reps=3):
@@ -56,6 +57,8 @@ rows = {
     "top_gainer": lambda: signals.top_gainer_features(o, h, l, c, v, qv),
     # the same inputs in one pass: the 21 values plus entry / status / score / stop_loss_pct
     "top_gainer_entry": lambda: signals.top_gainer_entry(o, h, l, c, v, qv),
+    # FailedSpikeFade.signal()'s pending-spike replay, every output column, no market masks
+    "spike_fade_replay": lambda: engine.spike_fade_replay(o, h, c, ts, spike_src),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
