@@ -257,6 +257,29 @@ TGE_VALUES = ("close", "open", "high", "low", "volume", "quote_volume", "previou
               "return_6h", "extension_return", "extension_window_bars", "extension_cap", "candle_return",
               "volume_ratio", "quote_volume_ratio", "range_position", "upper_wick_fraction", "ema20", "ema50", "atr")
 
+
+class BqSweepParams(ctypes.Structure):
+    """Mirror of ``bq_sweep_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("min_momentum_atr", ctypes.c_double), ("max_momentum_atr", ctypes.c_double),
+                ("min_close_location", ctypes.c_double), ("min_frame", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# bq_sweep_select: the gate columns in _is_candidate's order (:272-286), the status codes (BQ_SW_*, the index is
+# the code), the width below which a range runs a lane per row, the wide mapping's tile
+SW_COLUMNS = ("pump_score", "score_threshold", "momentum_atr", "close", "prior_high", "close_location",
+              "relative_volume", "volume_threshold", "trend_score", "ema20", "relative_strength", "btc_momentum_3",
+              "btc_trend_score")
+SW_REASONS = ("candidate", "frame_too_short", "required_value_not_finite", "no_score_cross",
+              "momentum_atr_out_of_range", "close_not_above_prior_high", "close_location_too_low",
+              "relative_volume_below_threshold", "trend_score_not_positive", "close_not_above_ema20",
+              "relative_strength_not_positive", "btc_momentum_not_positive", "btc_trend_not_positive",
+              "score_threshold_not_positive", "route_refused")
+BQ_SW_CANDIDATE, BQ_SW_SHORT_FRAME, BQ_SW_NOT_FINITE, BQ_SW_NO_CROSS = 0, 1, 2, 3
+BQ_SW_THRESHOLD_NONPOSITIVE, BQ_SW_ROUTE_REFUSED = 13, 14
+SW_NO_FRAME = BQ_SW_NO_FRAME = 255
+SW_SWITCH_WIDTH, SW_TILE, SW_ROW_CHUNK = 64, 256, 64
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
@@ -302,6 +325,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_top_gainer_default_params": (None, [ctypes.POINTER(BqTopGainerParams)]),
     "bq_top_gainer_entry": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64,
                                            ctypes.POINTER(BqTopGainerParams), _P, _P, _P, _P, _PP, _I64, _P]),
+    "bq_sweep_default_params": (None, [ctypes.POINTER(BqSweepParams)]),
+    "bq_sweep_select_workspace": (_I64, [_I64, _I64]),
+    "bq_sweep_select": (ctypes.c_int, [_PP, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64, _I64, _I64,
+                                       ctypes.POINTER(BqSweepParams), _P, _P, _I64, _P, _P, _P, _P]),
     "bq_retest_default_params": (None, [ctypes.POINTER(BqRetestParams)]),
     "bq_retest_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                         ctypes.POINTER(BqRetestParams), _P, _P, _P, _P, _P, _P, _I64, _P]),

@@ -22,7 +22,7 @@ all S symbols of the cohort in one call:
 * the 15m strategies' feature pipelines: LiquidationSweepPump,
   FailedSpikeFade, TopGainerEarlyMomentum, GradualGainerRetest's leadership
   (:445-499), and on request the decision bodies built on them (gates,
-  retest, top_entry, spike_fade below).
+  retest, top_entry, spike_fade, sweep below).
 
 Nothing reads back to the host, so the whole cohort can be captured once
 as a hipGraph (``graphs.CapturedPipeline(process_cohort, ...)``) and
@@ -69,7 +69,9 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                    gates: bool = False, retest: signals.RetestState | None = None,
                    retest_risk: torch.Tensor | None = None, top_entry: bool = False,
                    top_risk: torch.Tensor | None = None, spike_fade: signals.SpikeFadeState | None = None,
-                   spike_fade_market: tuple | None = None) -> dict[str, torch.Tensor]:
+                   spike_fade_market: tuple | None = None, sweep: bool = False,
+                   sweep_route: torch.Tensor | None = None,
+                   sweep_symbol_rank: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -109,8 +111,18 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     of signals.spike_fade_market_allows for that candle, each bool [T15] or
     one element (broadcast; both [S, T15] where the rows see different
     contexts), or None (allowed). Without a state the outputs
-    and launches are unchanged. Returns a flat dict of tensors (names
-    prefixed by the stage)."""
+    and launches are unchanged. sweep=True adds, after the pump stage and on
+    its stream, LiquidationSweepPump's decision for the cohort's message
+    (signals.liquidation_sweep_select on pump.* and c15 at the trigger column
+    T15 - 2 only: the newest candle is the message): sweep.status (uint8),
+    sweep.candidate (bool) and sweep.rank_score [S], and sweep.winner (int64,
+    the row the portfolio selector would dispatch, -1: none) /
+    sweep.winner_score, one element each. sweep_route: long_entry_routing's
+    verdict, bool [S] (or [S, T15]; None: allowed); sweep_symbol_rank: int32
+    [S] on the device, the rows' positions in the str order of their symbols
+    (None: the row index). Without sweep the outputs and launches are
+    unchanged. Returns a flat dict of tensors (names prefixed by the
+    stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -161,6 +173,19 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     def pump(out):   # :445-499
         for k, v in strategies.pump_score_features(o15, h15, l15, c15, v15, btc_c, exact=exact).items():
             out[f"pump.{k}"] = v
+        if sweep:   # signal()'s decision on df.iloc[-2] of the cohort's message, and the selector's pick
+            if T15 < 2:
+                raise ValueError("process_cohort: sweep needs T15 >= 2 (the trigger candle is T15 - 2)")
+            route = sweep_route
+            if route is not None and route.dim() == 1:
+                route = route.reshape(S, 1).expand(S, T15).contiguous()
+            u = T15 - 2
+            status, rank, winner, wscore = engine.sweep_select(
+                [c15 if k == "close" else out[f"pump.{k}"] for k in signals.SW_COLUMNS], out["pump.score_cross"],
+                route_ok=route, symbol_rank=sweep_symbol_rank, t_range=(u, u + 1))
+            out["sweep.status"], out["sweep.rank_score"] = status[:, u], rank[:, u]
+            out["sweep.candidate"] = out["sweep.status"] == 0
+            out["sweep.winner"], out["sweep.winner_score"] = winner[u:u + 1], wscore[u:u + 1]
 
     def spike(out):
         for k, v in strategies.failed_spike_features(o15, h15, l15, c15, v15, v15 * c15, exact=exact).items():

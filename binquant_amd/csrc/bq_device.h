@@ -26,6 +26,18 @@ __device__ __forceinline__ double win_val(double x) { return x - x == 0.0 ? x : 
 // that already select on their observation flag
 __device__ __forceinline__ bool win_ok(double x) { return x - x == 0.0; }
 
+// the order-preserving 64-bit image of a double (a < b <=> order_key(a) <
+// order_key(b), -0.0 below +0.0) and its inverse; key 0 never encodes a number
+__device__ __forceinline__ uint64_t order_key(double v) {
+  const uint64_t u = (uint64_t)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ double key_value(uint64_t k) {
+  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __longlong_as_double((long long)u);
+}
+
 // ---- compensated (double-double) accumulation ------------------------------
 struct dd {
   double hi, lo;

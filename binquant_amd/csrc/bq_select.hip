@@ -35,16 +35,6 @@ namespace bq {
 
 constexpr int SQ_NT = 256;
 
-__device__ __forceinline__ uint64_t order_key(double v) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double key_value(uint64_t k) {
-  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
 // block-wide sum of an int (all threads get the result)
 __device__ __forceinline__ int block_sum(int v, int* red) {
 #pragma unroll

@@ -1601,6 +1601,93 @@ def top_gainer_entry(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch
     return status, entry, sc, sl, outs
 
 
+SWEEP_DEFAULTS = dict(   # LiquidationSweepPump's class attributes (:94-101); min_frame: :314
+    min_momentum_atr=0.75, max_momentum_atr=3.0, min_close_location=0.70, min_frame=48 + 6 + 2)
+
+
+@device_entry
+def sweep_select(cols, score_cross: torch.Tensor, *, route_ok: torch.Tensor | None = None, first_t=None, lens=None,
+                 symbol_rank: torch.Tensor | None = None, t_range: tuple[int, int] | None = None,
+                 rank_score: bool = True, out: dict | None = None, **thresholds):
+    """LiquidationSweepPump's candidate gate and the cohort winner per candle
+    (strategies/liquidation_sweep_pump.py:271-343, :78-81; bq_sweep_select).
+    cols: the 13 [S, T] float64 columns of _lib.SW_COLUMNS, in that order (unit
+    stride along T, any common row pitch); score_cross [S, T] bool; route_ok
+    [S, T] bool (None: allowed); symbol_rank [S] int32 on the device (None:
+    the row index); t_range (t_lo, t_hi): the trigger-candle columns to
+    decide (None: all). Returns (status uint8 [S, T], rank_score float64
+    [S, T] or None, winner int64 [T], winner_score float64 [T]); columns
+    outside t_range are left as allocated (uninitialised), or as `out` holds
+    them: out = {"status", "rank_score", "winner", "winner_score"} reuses the
+    caller's tensors ([S, T] with one row pitch; [T]). Large panels get their
+    [S, T] outputs on enrich_outputs' padded pitch. thresholds:
+    SWEEP_DEFAULTS' keys."""
+    bad = set(thresholds) - set(SWEEP_DEFAULTS)
+    if bad:
+        raise ValueError(f"sweep_select: unknown thresholds {sorted(bad)} (known: {sorted(SWEEP_DEFAULTS)})")
+    par = {**SWEEP_DEFAULTS, **thresholds}
+    cols = list(cols)
+    if len(cols) != len(_lib.SW_COLUMNS):
+        raise ValueError(f"sweep_select: expected the {len(_lib.SW_COLUMNS)} columns {_lib.SW_COLUMNS}")
+    if not isinstance(cols[0], torch.Tensor) or cols[0].dim() != 2:
+        raise ValueError(f"{_lib.SW_COLUMNS[0]}: expected [S, T] with unit stride along T")
+    S, T = cols[0].shape
+    for x, name in zip(cols, _lib.SW_COLUMNS):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    masks = [(score_cross, "score_cross")] + ([(route_ok, "route_ok")] if route_ok is not None else [])
+    for m, name in masks:
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or tuple(m.shape) != (S, T):
+            raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)}")
+        if not m.is_cuda:
+            raise ValueError(f"{name}: expected a CUDA tensor (no CPU path)")
+    if symbol_rank is not None and (not isinstance(symbol_rank, torch.Tensor) or symbol_rank.dtype != torch.int32
+                                    or symbol_rank.numel() != S or not symbol_rank.is_cuda):
+        raise ValueError(f"symbol_rank: expected an int32 CUDA tensor of {S} entries")
+    t_lo, t_hi = (0, T) if t_range is None else (int(t_range[0]), int(t_range[1]))
+    if not 0 <= t_lo <= t_hi <= T:
+        raise ValueError(f"t_range: expected 0 <= t_lo <= t_hi <= {T}, got {(t_lo, t_hi)}")
+    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in zip(cols, _lib.SW_COLUMNS)])
+    score_cross = score_cross if T <= 1 or score_cross.stride(1) == 1 else score_cross.contiguous()
+    if route_ok is not None and T > 1 and route_ok.stride(1) != 1:
+        route_ok = route_ok.contiguous()
+    dev = cols[0].device
+    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
+    if symbol_rank is not None:
+        symbol_rank = symbol_rank.reshape(S).contiguous()
+    p = _lib.BqSweepParams()
+    for k in ("min_momentum_atr", "max_momentum_atr", "min_close_location"):
+        setattr(p, k, float(par[k]))
+    p.min_frame = int(par["min_frame"])
+    if out is None:
+        pad = ENRICH_ROW_PAD if S >= 1024 and T >= 1024 else 0
+        status = torch.empty((S, T + pad), dtype=torch.uint8, device=dev)[:, :T]
+        rs = torch.empty((S, T + pad), dtype=torch.float64, device=dev)[:, :T] if rank_score else None
+        winner = torch.empty((T,), dtype=torch.int64, device=dev)
+        wscore = torch.empty((T,), dtype=torch.float64, device=dev)
+    else:
+        status, rs, winner, wscore = out["status"], out.get("rank_score"), out["winner"], out["winner_score"]
+        ok = (status.dtype == torch.uint8 and tuple(status.shape) == (S, T) and (T <= 1 or status.stride(1) == 1)
+              and winner.dtype == torch.int64 and winner.numel() == T and winner.is_contiguous()
+              and wscore.dtype == torch.float64 and wscore.numel() == T and wscore.is_contiguous()
+              and (rs is None or (rs.dtype == torch.float64 and tuple(rs.shape) == (S, T)
+                                  and (T <= 1 or rs.stride(1) == 1) and _row_stride(rs) == _row_stride(status))))
+        if not ok:
+            raise ValueError("sweep_select: out tensors do not match the panel (dtype, shape or row pitch)")
+    lib = _lib.load()
+    work = torch.empty((max(int(lib.bq_sweep_select_workspace(S, T)), 8),), dtype=torch.uint8, device=dev)
+    st = lib.bq_sweep_select(
+        _lib.ptr_array([x.data_ptr() for x in cols]), ld_in, _ptr(score_cross), _row_stride(score_cross),
+        _ptr(route_ok), _row_stride(route_ok) if route_ok is not None else T, _ptr(lens), _ptr(first_t),
+        _ptr(symbol_rank), S, T, t_lo, t_hi, ctypes.byref(p), _ptr(status), _ptr(rs), _row_stride(status),
+        _ptr(winner), _ptr(wscore), _ptr(work), _stream_handle(None))
+    _lib.check(st, "bq_sweep_select")
+    return status, rs, winner, wscore
+
+
 RETEST_DEFAULTS = dict(   # GradualGainerRetest's class attributes (:78-85)
     watch_ms=8 * 3_600_000, min_history=100, breakout_lookback=8, support_factor=1 - 0.5 / 100,
     pullback_factor=1 - 0.04)

@@ -626,6 +626,92 @@ def top_gainer_risk_allows(market_stress_score, long_regime_score, short_regime_
     return reason == 0, reason
 
 
+# ---- LiquidationSweepPump: the candidate gate and the cohort winner -----------------------------------------------
+# bq_sweep_select's status codes: the first failing check of signal() in the method's order (:314, :287-299, :331,
+# :343); SW_REASONS names them (the reference returns silently, so the names are this library's)
+(SW_CANDIDATE, SW_SHORT_FRAME, SW_NOT_FINITE, SW_NO_CROSS, SW_MOMENTUM_ATR, SW_NOT_ABOVE_PRIOR_HIGH,
+ SW_CLOSE_LOCATION, SW_VOLUME, SW_TREND, SW_BELOW_EMA20, SW_RELATIVE_STRENGTH, SW_BTC_MOMENTUM, SW_BTC_TREND,
+ SW_THRESHOLD_NONPOSITIVE, SW_ROUTE_REFUSED) = range(15)
+SW_NO_FRAME = _lib.SW_NO_FRAME   # u + 1 >= lens[s] or u < first_t[s]: no such message (not a reference outcome)
+SW_REASONS = dict(enumerate(_lib.SW_REASONS))
+SW_COLUMNS = _lib.SW_COLUMNS     # the 13 values _is_candidate requires, in its order; plus "score_cross"
+
+
+def liquidation_sweep_select(cols, *, close=None, route_ok=None, first_t=None, lens=None, symbol_rank=None,
+                             t_range=None, params=None):
+    """LiquidationSweepPump.signal() between compute_pump_score and the
+    portfolio selector (strategies/liquidation_sweep_pump.py:302-343), and the
+    selector's pick per candle time (:78-81), for every trigger candle of the
+    panel in one call (engine.sweep_select, bq_sweep_select).
+
+    cols: the dict strategies.pump_score_features returns, or any mapping with
+    SW_COLUMNS' 13 keys and "score_cross" ([S, T]); pump_score_features does
+    not return the frame's own close, so it is taken from cols["close"] or
+    from `close=`. Column u is the TRIGGER candle — the decision signal()
+    takes on df.iloc[-2] at the message whose frame is df.iloc[first_t[s] :
+    u + 2]; the rows share one open-time grid, so a column is one cohort of
+    the selector. route_ok [S, T] bool: long_entry_routing's verdict per cell
+    (sweep_routing_allows; None: allowed). symbol_rank [S] int32 on the
+    device: each row's position in the str order of the symbol names — the
+    selector's tie-break is max(key=(rank_score, symbol)) (None: the row
+    index). t_range (t_lo, t_hi): decide these columns only; the others'
+    outputs are not written (uninitialised). params: engine.SWEEP_DEFAULTS'
+    keys.
+
+    Returns {"status": uint8 [S, T] (SW_* codes, SW_REASONS their names; 0 =
+    the candidate signal() submits; SW_NO_FRAME where there is no such
+    message), "candidate": bool [S, T] (status == 0), "rank_score": float64
+    [S, T], pump_score / score_threshold where status == 0 and NaN elsewhere,
+    "winner": int64 [T], the row _dispatch_winner dispatches for that candle
+    time or -1, "winner_score": float64 [T], its rank_score or NaN}. Status,
+    rank_score and the winner are exact given the columns. What stays on the
+    host: the message text, observe() / the cohorts' bookkeeping and the
+    dispatch."""
+    missing = [k for k in SW_COLUMNS + ("score_cross",) if k not in cols and not (k == "close" and close is not None)]
+    if missing:
+        raise ValueError(f"liquidation_sweep_select: missing columns {missing}")
+    cs = [close if k == "close" and close is not None else cols[k] for k in SW_COLUMNS]
+    status, rank, winner, wscore = engine.sweep_select(cs, cols["score_cross"], route_ok=route_ok, first_t=first_t,
+                                                       lens=lens, symbol_rank=symbol_rank, t_range=t_range,
+                                                       **(params or {}))
+    return {"status": status, "candidate": status == 0, "rank_score": rank, "winner": winner,
+            "winner_score": wscore}
+
+
+# LiquidationSweepPump.long_entry_routing's reasons (:164-193) as uint8 codes: the refusals in the method's order,
+# then the accepting route
+SW_ROUTE_REASONS = ("market_context_unavailable", "market_stress_too_high", "market_breadth_not_washed_out",
+                    "market_breadth_not_recovering", "btc_not_increasing", "symbol_regime_unavailable",
+                    "symbol_trend_not_up", "market_breadth_recovering_btc_up_symbol_up")
+SW_ROUTE_OK = len(SW_ROUTE_REASONS) - 1
+
+
+def sweep_routing_allows(market_stress_score, market_breadth, market_breadth_recovery, context_ok, btc_momentum,
+                         symbol_trend_score, features_ok, max_market_stress: float = 0.35,
+                         breadth_threshold: float = -0.2, min_breadth_recovery: float = 0.02):
+    """LiquidationSweepPump.long_entry_routing (strategies/liquidation_sweep_pump.py
+    :164-193) per (symbol, candle): the context's market_stress_score, the
+    latest market breadth and its recovery values[-1] - values[-3] ([T] or
+    [S, T] float64; a NaN recovery is the method's None: fewer than three
+    breadth values) and context_ok bool (False: no context); btc_momentum
+    [S, T] float64 (the trigger row's btc_momentum_3), symbol_trend_score
+    [S, T] float64 and features_ok [S, T] bool (False: the context has no
+    features for the symbol). Returns (ok bool [S, T], reason uint8 [S, T]):
+    the first refusing check in the method's order, SW_ROUTE_REASONS its
+    strings (SW_ROUTE_OK = the accepting route). One fused element-wise
+    program. _market_breadth_values' timestamp parsing and sorting of the API
+    series (:135-153) is a host step: the caller passes the sorted series'
+    last value and recovery, or the context's advancers - decliners."""
+    S, T = symbol_trend_score.shape
+    STRESS, BREADTH, REC = F.inp(market_stress_score), F.inp(market_breadth), F.inp(market_breadth_recovery)
+    BTC, TREND = F.inp(btc_momentum), F.inp(symbol_trend_score)
+    code = _first_true([(~F.inp(context_ok), 0), (STRESS >= max_market_stress, 1), (BREADTH > breadth_threshold, 2),
+                        (F.isnan(REC) | (REC < min_breadth_recovery), 3), (BTC <= 0.0, 4),
+                        (~F.inp(features_ok), 5), (TREND <= 0.0, 6)], float(SW_ROUTE_OK))
+    reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
+    return reason == SW_ROUTE_OK, reason
+
+
 def bb_width_stable(bb_upper, bb_mid, bb_lower, n: int = 8, max_change_pct: float = 20.0, *, first_t=None,
                     lens=None) -> dict[str, torch.Tensor]:
     """LadderDeployer._bb_stable(n, max_change_pct) evaluated at every t

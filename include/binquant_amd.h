@@ -56,6 +56,10 @@
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
+ *   bq_sweep_select    <- LiquidationSweepPump.signal() between compute_pump_score and
+ *                         the selector: the frame gate, _is_candidate, rank_score,
+ *                         the routing verdict, and _dispatch_winner's pick per candle
+ *                         (strategies/liquidation_sweep_pump.py:271-343, :78-81)
  *   bq_breadth_partial <- the per-symbol sums/counts of
  *                         LiveMarketContextAccumulator._build_context
  *                         market_regime/live_market_context_accumulator.py:135-163
@@ -640,6 +644,91 @@ int bq_top_gainer_entry(const double* open, const double* high, const double* lo
                         const int64_t* lens, const int64_t* first_t, int64_t S, int64_t T,
                         const bq_top_gainer_params* params, uint8_t* status, uint8_t* entry, double* score,
                         double* stop_loss_pct, double* const* values, int64_t ld_out, void* stream);
+
+/*
+ * LiquidationSweepPump's candidate gate and the cohort winner at every candle
+ * of the panel (strategies/liquidation_sweep_pump.py): what signal() does
+ * between compute_pump_score and the portfolio selector (:302-343), and the
+ * pick LiquidationSweepPortfolioSelector._dispatch_winner makes among a candle
+ * time's candidates (:78-81).
+ *
+ * cols: BQ_SW_NCOLS device pointers (a host table), each [S][ld_in] fp64, the
+ * values _is_candidate reads in its order (:272-286): pump_score,
+ * score_threshold, momentum_atr, close, prior_high, close_location,
+ * relative_volume, volume_threshold, trend_score, ema20, relative_strength,
+ * btc_momentum_3, btc_trend_score. score_cross [S][ld_b] bytes. route_ok
+ * [S][ld_r] bytes, long_entry_routing's verdict per cell (:338-343; NULL:
+ * allowed). lens / first_t [S] (NULL: T / 0). symbol_rank [S]: the position of
+ * the row's symbol in the str order of the names (NULL: the row index).
+ *
+ * Column u is the TRIGGER candle: the decision signal() takes on df.iloc[-2]
+ * at the message whose frame is df.iloc[first : u + 2] (the newest candle
+ * u + 1 is the message). Domain: the rows share one open-time grid, so column
+ * u of every row is one candle time — one cohort of the selector (the cohort
+ * stage assumes the same); the columns are the caller's, computed on frames
+ * that start at `first` (the panel convention of the pump features). Only
+ * columns of [t_lo, t_hi) are read or written.
+ *
+ * status [S][ld_out] bytes: the first failing check in the method's order
+ * (BQ_SW_*): NO_FRAME where u + 1 >= lens[s] or u < first; SHORT_FRAME where
+ * u + 2 - first < min_frame (:314); NOT_FINITE (:287); the score cross and
+ * the nine compares of :290-299, each in the method's direction;
+ * THRESHOLD_NONPOSITIVE (:331); ROUTE_REFUSED (:343); else 0, a candidate the
+ * method would submit. rank_score [S][ld_out] fp64 (NULL = skip): pump_score /
+ * score_threshold, one correctly rounded divide (:333), where status is 0; NaN
+ * elsewhere.
+ *
+ * winner / winner_score [T] (winner_score NULL = skip): per column the row of
+ * the candidate with the largest (rank_score, symbol_rank) — max(key=
+ * (rank_score, symbol)) of :78-81 — and its rank_score; -1 / NaN for a column
+ * without a candidate. Equal ranks are a caller error (two rows, one symbol);
+ * then the larger row wins. A rank_score that overflowed to +inf beats every
+ * finite one. The result does not depend on the launch geometry.
+ *
+ * workspace: bq_sweep_select_workspace(S, T) bytes of device memory, 8-byte
+ * aligned, the caller's; no initialisation needed, nothing is allocated.
+ * Ranges of fewer than 64 columns (the cohort's one column) run a lane per
+ * row, wider ones (the panel replay) a lane per candle.
+ *
+ * params NULL: the class attributes (bq_sweep_default_params). BQ_EINVAL,
+ * before any launch: cols or an entry of it NULL; score_cross, status, winner
+ * or workspace NULL (or workspace misaligned); ld_in, ld_b or ld_out < T, ld_r
+ * < T with route_ok given; t_lo < 0, t_hi > T, t_lo > t_hi; a non-finite
+ * threshold or min_momentum_atr > max_momentum_atr; S or T above 0x7fffffff
+ * (or a range whose workgroup count is). S == 0, T == 0 or t_lo == t_hi:
+ * BQ_OK, no launch.
+ */
+#define BQ_SW_NCOLS 13
+#define BQ_SW_CANDIDATE               0   /* submitted to the selector (:438) */
+#define BQ_SW_SHORT_FRAME             1   /* len(df) < SCORE_LOOKBACK + COMPRESSION_BARS + 2 (:314) */
+#define BQ_SW_NOT_FINITE              2   /* a required value is not finite (:287) */
+#define BQ_SW_NO_CROSS                3   /* score_cross (:290) */
+#define BQ_SW_MOMENTUM_ATR            4   /* MIN <= momentum_atr <= MAX (:291) */
+#define BQ_SW_NOT_ABOVE_PRIOR_HIGH    5   /* close > prior_high (:292) */
+#define BQ_SW_CLOSE_LOCATION          6   /* close_location >= MIN_CLOSE_LOCATION (:293) */
+#define BQ_SW_VOLUME                  7   /* relative_volume >= volume_threshold (:294) */
+#define BQ_SW_TREND                   8   /* trend_score > 0 (:295) */
+#define BQ_SW_BELOW_EMA20             9   /* close > ema20 (:296) */
+#define BQ_SW_RELATIVE_STRENGTH      10   /* relative_strength > 0 (:297) */
+#define BQ_SW_BTC_MOMENTUM           11   /* btc_momentum_3 > 0 (:298) */
+#define BQ_SW_BTC_TREND              12   /* btc_trend_score > 0 (:299) */
+#define BQ_SW_THRESHOLD_NONPOSITIVE  13   /* score_threshold <= 0 (:331) */
+#define BQ_SW_ROUTE_REFUSED          14   /* long_entry_routing refused (:343) */
+#define BQ_SW_NO_FRAME              255   /* u + 1 >= lens[s] or u < first: no such message */
+typedef struct bq_sweep_params {
+  double min_momentum_atr;     /* MIN_MOMENTUM_ATR 0.75 */
+  double max_momentum_atr;     /* MAX_MOMENTUM_ATR 3.0 */
+  double min_close_location;   /* MIN_CLOSE_LOCATION 0.70 */
+  int32_t min_frame;           /* SCORE_LOOKBACK + COMPRESSION_BARS + 2 = 56 (:314) */
+  int32_t reserved;
+} bq_sweep_params;
+void bq_sweep_default_params(bq_sweep_params* p);
+int64_t bq_sweep_select_workspace(int64_t S, int64_t T);
+int bq_sweep_select(const double* const* cols, int64_t ld_in, const uint8_t* score_cross, int64_t ld_b,
+                    const uint8_t* route_ok, int64_t ld_r, const int64_t* lens, const int64_t* first_t,
+                    const int32_t* symbol_rank, int64_t S, int64_t T, int64_t t_lo, int64_t t_hi,
+                    const bq_sweep_params* params, uint8_t* status, double* rank_score, int64_t ld_out,
+                    int64_t* winner, double* winner_score, void* workspace, void* stream);
 
 /* ---- benchmark-relative statistics ---------------------------------------- */
 /*

@@ -24,6 +24,21 @@ atr = engine.enrich(o, h, l, c, v, columns=("ATR",))["ATR"]
 spike_src = torch.rand(S, T, device="cuda") < 0.05   # a source_ok mask of the failed-spike-fade replay
 
 
+_pump: dict = {}
+
+
+def sweep_cols():
+    """The 13 gate columns of bq_sweep_select, computed once: the pump pipeline's outputs and the close."""
+    if not _pump:
+        _pump.update(strategies.pump_score_features(o, h, l, c, v, btc))
+    return [c if k == "close" else _pump[k] for k in signals.SW_COLUMNS]
+
+
+def sweep_cross():
+    sweep_cols()
+    return _pump["score_cross"]
+
+
 def timeit(fn, reps=3):
     fn()
     torch.cuda.synchronize()
@@ -59,6 +74,8 @@ rows = {
     "top_gainer_entry": lambda: signals.top_gainer_entry(o, h, l, c, v, qv),
     # FailedSpikeFade.signal()'s pending-spike replay, every output column, no market masks
     "spike_fade_replay": lambda: engine.spike_fade_replay(o, h, c, ts, spike_src),
+    # LiquidationSweepPump's gate and the cohort winner per candle: the kernel alone over the pump columns, all outputs
+    "sweep_select": lambda: engine.sweep_select(sweep_cols(), sweep_cross()),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
