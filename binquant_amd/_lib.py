@@ -225,6 +225,34 @@ BQ_FS_NO_FRAME = 255
 FS_EVENTS = ("idle", "source_set", "waiting", "candidate", "cleared", "same_candle")
 
 
+class BqPriceTrackerParams(ctypes.Structure):
+    """Mirror of ``bq_price_tracker_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("min_history", ctypes.c_int32), ("tail_rows", ctypes.c_int32), ("span_fast", ctypes.c_int32),
+                ("span_slow", ctypes.c_int32), ("rsi_max", ctypes.c_double), ("macd_max", ctypes.c_double),
+                ("mfi_max", ctypes.c_double), ("w_rsi", ctypes.c_double), ("w_mfi", ctypes.c_double),
+                ("w_macd", ctypes.c_double), ("macd_scale", ctypes.c_double), ("context_weight", ctypes.c_double),
+                ("risk_weight", ctypes.c_double), ("support_weight", ctypes.c_double),
+                ("min_followthrough", ctypes.c_double), ("max_risk", ctypes.c_double),
+                ("min_confidence", ctypes.c_double), ("cooldown_ms", ctypes.c_int64)]
+
+
+# bq_price_tracker_replay: status codes (BQ_PT_*, the index is the code; the reference returns silently, so the
+# names are this library's), detail bits (BQ_PT_D_*), the value columns' order, the context rows' order
+PT_MAX_TAIL_ROWS = 64
+(BQ_PT_EMIT, BQ_PT_NO_FRAME, BQ_PT_NOT_READY, BQ_PT_NO_SETUP, BQ_PT_NO_CONTEXT, BQ_PT_CONTEXT_REJECTED,
+ BQ_PT_COOLDOWN) = range(7)
+BQ_PT_D_FOLLOWTHROUGH, BQ_PT_D_RISK, BQ_PT_D_CONFIDENCE = 1, 2, 4
+PT_REASONS = ("emit", "no_frame", "not_enough_data", "not_oversold", "market_context_unavailable",
+              "context_rejected", "entry_cooldown_active")
+PT_DETAILS = {BQ_PT_D_FOLLOWTHROUGH: "bad_followthrough", BQ_PT_D_RISK: "high_risk",
+              BQ_PT_D_CONFIDENCE: "low_confidence"}
+PT_VALUES = ("local_score", "trend_score", "followthrough", "adverse_risk", "supportiveness", "adjusted_score")
+PT_CTX_ROWS = ("confidence", "long_tailwind", "btc_regime_score", "market_stress_score")
+# LiveMarketContext.market_regime's literals (market_regime/models.py:7-13), the index is the code
+MARKET_REGIMES = ("TREND_UP", "TREND_DOWN", "RANGE", "HIGH_STRESS", "TRANSITIONAL")
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -335,6 +363,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_spike_fade_default_params": (None, [ctypes.POINTER(BqSpikeFadeParams)]),
     "bq_spike_fade_replay": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                             ctypes.POINTER(BqSpikeFadeParams), _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "bq_price_tracker_default_params": (None, [ctypes.POINTER(BqPriceTrackerParams)]),
+    "bq_price_tracker_replay": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64,
+                                               _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64,
+                                               ctypes.POINTER(BqPriceTrackerParams), _P, _P, _P, _P, _PP, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

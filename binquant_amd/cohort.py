@@ -12,7 +12,8 @@ pipelines 9.1 / 9.8 / 24.3). ``process_cohort`` runs the same device work for
 all S symbols of the cohort in one call:
 
 * 5m frame: indicators_enrichment (bq_enrich, the 14 columns, :367-369) and
-  ActivityBurstPump's features (:380-388);
+  ActivityBurstPump's features (:380-388), and on request the two 5m
+  strategies' decisions (price_tracker, burst_entry below);
 * 15m frame: indicators_enrichment (:415), the 1h resample (:403-407, a9),
   dynamic_btc_beta_corr (:424, a11: index-aligned frames) and the BTC
   pct_change(96) (:425-428, a12);
@@ -71,7 +72,10 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                    top_risk: torch.Tensor | None = None, spike_fade: signals.SpikeFadeState | None = None,
                    spike_fade_market: tuple | None = None, sweep: bool = False,
                    sweep_route: torch.Tensor | None = None,
-                   sweep_symbol_rank: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+                   sweep_symbol_rank: torch.Tensor | None = None,
+                   price_tracker: signals.PriceTrackerState | None = None, ct5: torch.Tensor | None = None,
+                   price_tracker_ctx: tuple | None = None, price_tracker_rs: torch.Tensor | None = None,
+                   burst_entry: bool = False, burst_route: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -121,8 +125,25 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     verdict, bool [S] (or [S, T15]; None: allowed); sweep_symbol_rank: int32
     [S] on the device, the rows' positions in the str order of their symbols
     (None: the row index). Without sweep the outputs and launches are
-    unchanged. Returns a flat dict of tensors (names prefixed by the
-    stage)."""
+    unchanged. price_tracker: the cohort's PriceTracker cooldown entries
+    (signals.PriceTrackerState, [S]): the decisions of its signal() (:165-251
+    of the strategy) run on the newest 5m candle, after the 5m frame's
+    enrichment and on its stream, from e5.rsi / e5.macd / e5.mfi, the 5m
+    panel and ct5 (the 5m close_time, int64 [S, T5]), from that state, which
+    is updated in place (a captured graph carries it from message to message);
+    pricetracker.status / detail / local_score / adjusted_score [S] are
+    added. price_tracker_ctx: (ctx float64 [4, 1], ctx_ok bool / uint8 [1] or
+    None) of signals.price_tracker_entry, device tensors the caller updates in
+    place between replays; price_tracker_rs: the snapshot's
+    relative_strength_vs_btc per row, float64 [S] (None: 0.0, no symbol is in
+    the snapshot). burst_entry=True adds ActivityBurstPump.signal()'s verdict
+    for the newest 5m candle (signals.activity_burst_entry on
+    burst.qualified_signal): burst.entry_status (uint8) / burst.autotrade
+    (bool) [S]. burst_route: allows_long_autotrade per row, bool [S] (or
+    [S, T5]; signals.long_autotrade_allows), or None: latest_market_context is
+    None (the message goes out without autotrade). Without these keywords the
+    outputs and launches are unchanged. Returns a flat dict of tensors (names
+    prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -132,6 +153,26 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
             out[f"e5.{k}"] = v
         for k, v in strategies.activity_burst_features(o5, h5, l5, c5, v5, v5 * c5).items():
             out[f"burst.{k}"] = v
+        T5, dev = c5.shape[1], c5.device
+        if price_tracker is not None:   # signal()'s decisions on the cohort's message: the newest candle only
+            if ct5 is None or price_tracker_ctx is None:
+                raise ValueError("process_cohort: price_tracker needs ct5 and price_tracker_ctx")
+            ctx, ctx_ok = price_tracker_ctx
+            rs = price_tracker_rs if price_tracker_rs is not None else torch.zeros(S, dtype=torch.float64, device=dev)
+            newest = torch.full((S,), T5 - 1, dtype=torch.int64, device=dev)
+            pt = signals.price_tracker_entry(c5, out["e5.rsi"], out["e5.macd"], out["e5.mfi"], ct5, rs, ctx, ctx_ok,
+                                             h=h5, l=l5, v=v5, state=price_tracker, from_t=newest,
+                                             columns=("local_score", "adjusted_score"))
+            for k in ("status", "detail", "local_score", "adjusted_score"):
+                out[f"pricetracker.{k}"] = pt[k][:, -1]
+        if burst_entry:   # signal()'s frame gate, routing and qualified_signal (:164-185) on the newest candle
+            present = burst_route is not None
+            route = burst_route if present else torch.ones((S, 1), dtype=torch.bool, device=dev)
+            if route.dim() == 1:
+                route = route.reshape(S, 1)
+            be = signals.activity_burst_entry(out["burst.qualified_signal"], route,
+                                              torch.full((1,), present, dtype=torch.bool, device=dev))
+            out["burst.entry_status"], out["burst.autotrade"] = be["status"][:, -1], be["autotrade"][:, -1]
 
     def frame_15m(out):   # :402-432
         for k, v in engine.enrich(o15, h15, l15, c15, v15).items():

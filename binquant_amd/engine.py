@@ -1862,6 +1862,123 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
     return event, det, brs
 
 
+PRICE_TRACKER_DEFAULTS = dict(   # PriceTracker.signal()'s constants and class attributes (:34-35, :59-63, :177-239)
+    min_history=30, tail_rows=5, span_fast=9, span_slow=21, rsi_max=30.0, macd_max=0.0, mfi_max=20.0, w_rsi=0.35,
+    w_mfi=0.35, w_macd=0.3, macd_scale=100.0, context_weight=0.35, risk_weight=0.35, support_weight=0.2,
+    min_followthrough=-0.2, max_risk=0.6, min_confidence=0.5, cooldown_ms=12 * 300_000)
+_PT_INT_PARAMS = ("min_history", "tail_rows", "span_fast", "span_slow", "cooldown_ms")
+
+
+@device_entry
+def price_tracker_replay(c: torch.Tensor, rsi: torch.Tensor, macd: torch.Tensor, mfi: torch.Tensor,
+                         close_time: torch.Tensor, symbol_rs: torch.Tensor, ctx: torch.Tensor,
+                         ctx_ok: torch.Tensor | None = None, *, h: torch.Tensor | None = None,
+                         l: torch.Tensor | None = None, v: torch.Tensor | None = None,
+                         trend_score: torch.Tensor | None = None, state=None, first_t=None, lens=None, from_t=None,
+                         detail: bool = True, columns=_lib.PT_VALUES, **params):
+    """PriceTracker.signal() replayed over the panel
+    (strategies/coinrule/price_tracker.py:165-324; bq_price_tracker_replay):
+    column t of row s = the method on the message whose frame is
+    df.iloc[first_t[s]:t + 1], after the messages of all earlier candles;
+    candles max(from_t[s], first_t[s]) .. lens[s] - 1 are replayed. c / rsi /
+    macd / mfi (and h / l / v, read by the null test only; None: no NaN in
+    them) [S, T] float64 with unit stride along T and any row pitch,
+    mfi[s, t] = Indicators.mfi of the frame ending at t; close_time [S, T]
+    int64 ms, strictly ascending within a row's frame. trend_score [S, T] or
+    None: the EMA 9 / 21 score formed in the pass. symbol_rs float64 [S] or
+    [S, T]; ctx float64 [4, Tc] (_lib.PT_CTX_ROWS), Tc 1 or T, and ctx_ok
+    bool / uint8 [Tc] (None: present), on the device. state: None (no entry,
+    discard) or the (has uint8, last_close_time int64) [S] tensors, updated in
+    place. Returns (status uint8 [S, T] (_lib.BQ_PT_*), detail uint8 [S, T] or
+    None, {name: float64 [S, T]} for `columns`, a subset of _lib.PT_VALUES,
+    NaN where the method did not reach them). params: PRICE_TRACKER_DEFAULTS'
+    keys (cooldown_ms 0: strategy_cooldowns is None)."""
+    bad = set(params) - set(PRICE_TRACKER_DEFAULTS)
+    if bad:
+        raise ValueError(f"price_tracker_replay: unknown parameters {sorted(bad)} "
+                         f"(known: {sorted(PRICE_TRACKER_DEFAULTS)})")
+    par = {**PRICE_TRACKER_DEFAULTS, **params}
+    for k, val in par.items():
+        if k not in _PT_INT_PARAMS and not math.isfinite(float(val)):
+            raise ValueError(f"price_tracker_replay: {k} must be finite, got {val}")
+    if int(par["min_history"]) < 1 or not 1 <= int(par["tail_rows"]) <= _lib.PT_MAX_TAIL_ROWS:
+        raise ValueError(f"price_tracker_replay: min_history >= 1 and tail_rows in 1..{_lib.PT_MAX_TAIL_ROWS}")
+    if int(par["span_fast"]) < 1 or int(par["span_slow"]) < 1 or int(par["cooldown_ms"]) < 0:
+        raise ValueError("price_tracker_replay: spans must be >= 1 and cooldown_ms >= 0")
+    if float(par["rsi_max"]) == 0.0 or float(par["mfi_max"]) == 0.0:
+        raise ValueError("price_tracker_replay: rsi_max and mfi_max divide local_score's terms: not 0")
+    unknown = [k for k in columns if k not in _lib.PT_VALUES]
+    if unknown:
+        raise ValueError(f"price_tracker_replay: unknown columns {unknown} (known: {_lib.PT_VALUES})")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    px = [(c, "close")] + [(x, n) for x, n in ((h, "high"), (l, "low"), (v, "volume")) if x is not None]
+    ind = [(rsi, "rsi"), (macd, "macd"), (mfi, "mfi")]
+    opt = [(trend_score, "trend_score")] if trend_score is not None else []
+    for x, name in px + ind + opt:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    if not isinstance(close_time, torch.Tensor) or close_time.dtype != torch.int64 or tuple(close_time.shape) != (S, T):
+        raise ValueError(f"close_time: expected an int64 tensor of shape {(S, T)}")
+    if (not isinstance(symbol_rs, torch.Tensor) or symbol_rs.dtype != torch.float64
+            or tuple(symbol_rs.shape) not in ((S,), (S, T))):
+        raise ValueError(f"symbol_rs: expected a float64 tensor of shape {(S,)} or {(S, T)}")
+    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
+            or ctx.shape[0] != len(_lib.PT_CTX_ROWS) or ctx.shape[1] not in (1, T)):
+        raise ValueError(f"ctx: expected a float64 tensor of shape (4, 1) or {(4, T)} (rows {_lib.PT_CTX_ROWS})")
+    Tc = int(ctx.shape[1])
+    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
+                               or tuple(ctx_ok.shape) != (Tc,)):
+        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
+    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
+        _gate_rows(from_t, "from_t", S)
+    if state is not None:
+        if len(state) != 2:
+            raise ValueError("state: expected (has, last_close_time)")
+        for x, name, dt in zip(state, ("state.has", "state.last_close_time"), (torch.uint8, torch.int64)):
+            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    pxs, ld_px = _common_pitch([_check_panel(x, n) for x, n in px])
+    inds, ld_ind = _common_pitch([_check_panel(x, n) for x, n in ind])
+    tr = _check_panel(trend_score, "trend_score") if trend_score is not None else None
+    ct = _check_ts(close_time, "close_time")
+    others = [symbol_rs, ctx] + ([ctx_ok] if ctx_ok is not None else []) + list(state or ())
+    if not all(x.is_cuda for x in others):
+        raise ValueError("symbol_rs / ctx / ctx_ok / state: expected CUDA tensors (no CPU path)")
+    if symbol_rs.dim() == 2:
+        symbol_rs = _check_panel(symbol_rs, "symbol_rs")
+        ld_rs = _row_stride(symbol_rs)
+    else:
+        symbol_rs, ld_rs = symbol_rs.contiguous(), 0
+    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
+        ctx = ctx.contiguous()
+    ld_ctx = int(ctx.stride(0))
+    if ctx_ok is not None and not ctx_ok.is_contiguous():
+        ctx_ok = ctx_ok.contiguous()
+    cc, rest = pxs[0], iter(pxs[1:])
+    hh, ll, vv = (next(rest) if x is not None else None for x in (h, l, v))
+    dev = c.device
+    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    p = _lib.BqPriceTrackerParams()
+    for k, val in par.items():
+        setattr(p, k, int(val) if k in _PT_INT_PARAMS else float(val))
+    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    det = torch.empty((S, T), dtype=torch.uint8, device=dev) if detail else None
+    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
+    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.PT_VALUES])
+    sh, sl = state if state is not None else (None, None)
+    st = _lib.load().bq_price_tracker_replay(
+        _ptr(cc), _ptr(hh), _ptr(ll), _ptr(vv), ld_px, _ptr(inds[0]), _ptr(inds[1]), _ptr(inds[2]), ld_ind, _ptr(ct), T,
+        _ptr(tr), _row_stride(tr) if tr is not None else T, _ptr(symbol_rs), ld_rs, _ptr(ctx), ld_ctx, _ptr(ctx_ok), Tc,
+        _ptr(lens), _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(sh), _ptr(sl), _ptr(status), _ptr(det),
+        vals, T, _stream_handle(None))
+    _lib.check(st, "bq_price_tracker_replay")
+    return status, det, outs
+
+
 def _join_capacity(ts: torch.Tensor, lens: torch.Tensor | None, bts: torch.Tensor) -> int:
     """Largest per-row count of (candle, benchmark row) matches over the
     candles t >= 1 that join (bench_ts ascending): an upper bound on every

@@ -36,6 +36,16 @@ prefix frame df.iloc[:t + 1]:
                      state machine replayed per row (bq_spikefade.hip), with
                      spike_source_allows (:190-203) and
                      spike_fade_market_allows (:155-188)
+* price_tracker_entry  the decisions of PriceTracker.signal()
+                     (strategies/coinrule/price_tracker.py:165-251) on the 5m
+                     frame: null gate, oversold test, local and context
+                     score, the three rejections and the entry cooldown, one
+                     pass (bq_pricetracker.hip), with price_tracker_routing
+                     for regime_routing (:113-163)
+* activity_burst_entry  ActivityBurstPump.signal()'s frame gate, routing and
+                     qualified_signal (strategies/activity_burst_pump.py:160-185),
+                     with long_autotrade_allows for allows_long_autotrade
+                     (market_regime/regime_routing.py:30-75)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -743,3 +753,216 @@ def mean_reversion_features(o, h, l, c, v, atr, rsi_window: int = 14, volume_ma_
     })
     return {"rsi": res["rsi"], "previous_rsi": res["previous_rsi"], "volume_ma": vma, "atr_ma": ama,
             "trend_score": res["trend_score"], "upper_rejection_ratio": res["upper_rejection_ratio"]}
+
+
+# ---- the 5m strategies: PriceTracker and ActivityBurstPump --------------------------------------------------------
+# bq_price_tracker_replay's status codes: where PriceTracker.signal() returned, in the method's order (the
+# reference returns silently: PT_REASONS' names are this library's), and the rejection's detail bits
+(PT_EMIT, PT_NO_FRAME, PT_NOT_READY, PT_NO_SETUP, PT_NO_CONTEXT, PT_CONTEXT_REJECTED, PT_COOLDOWN) = range(7)
+PT_REASONS = dict(enumerate(_lib.PT_REASONS))
+PT_D_FOLLOWTHROUGH, PT_D_RISK, PT_D_CONFIDENCE = (_lib.BQ_PT_D_FOLLOWTHROUGH, _lib.BQ_PT_D_RISK,
+                                                  _lib.BQ_PT_D_CONFIDENCE)
+PT_VALUES = _lib.PT_VALUES
+PT_CTX_ROWS = _lib.PT_CTX_ROWS
+
+
+class PriceTrackerState:
+    """PriceTracker's entries of strategy_cooldowns for S rows: has uint8 (the
+    (ALGO, symbol) key is present) and last_close_time int64 (ms), each [S] on
+    the device. signals.price_tracker_entry / engine.price_tracker_replay
+    update it in place, so a captured graph carries it from one message to
+    the next."""
+
+    __slots__ = ("has", "last_close_time")
+
+    def __init__(self, has: torch.Tensor, last_close_time: torch.Tensor):
+        self.has, self.last_close_time = has, last_close_time
+
+    @classmethod
+    def empty(cls, S: int, device) -> "PriceTrackerState":
+        return cls(torch.zeros(S, dtype=torch.uint8, device=device), torch.zeros(S, dtype=torch.int64, device=device))
+
+    def clone(self) -> "PriceTrackerState":
+        return PriceTrackerState(self.has.clone(), self.last_close_time.clone())
+
+    def tensors(self) -> tuple[torch.Tensor, torch.Tensor]:
+        return self.has, self.last_close_time
+
+
+def price_tracker_entry(c, rsi, macd, mfi, close_time, symbol_rs, ctx, ctx_ok=None, *, h=None, l=None, v=None,
+                        trend_score=None, state: PriceTrackerState | None = None, first_t=None, lens=None,
+                        from_t=None, columns=PT_VALUES, **params):
+    """The decisions of PriceTracker.signal() (strategies/coinrule/price_tracker.py
+    :165-251) for every candle of a 5m panel in one pass
+    (engine.price_tracker_replay, bq_price_tracker_replay). Column t of row s
+    = the method on the message whose frame is df.iloc[first_t[s]:t + 1],
+    after the messages of all earlier candles; candles from_t[s] ..
+    lens[s] - 1 are replayed, from `state` (None: no cooldown entry), which is
+    updated in place. c / rsi / macd / mfi [S, T] float64 (engine.enrich's
+    columns; mfi's column t is Indicators.mfi of the frame ending at t), h / l
+    / v only for the tail(5).isnull() test (None: no NaN in them), close_time
+    [S, T] int64 ms. trend_score: the method's EMA 9 / 21 score [S, T], or
+    None to form it in the pass (1e-9 of pandas). symbol_rs [S] or [S, T]: the
+    context snapshot's relative_strength_vs_btc of the symbol, 0.0 where it
+    has none. ctx [4, 1] or [4, T] float64 (PT_CTX_ROWS) and ctx_ok [1] / [T]
+    (False: latest_market_context is None), both on the device. params:
+    engine.PRICE_TRACKER_DEFAULTS' keys.
+
+    Returns {"status": uint8 [S, T] (PT_* codes, PT_REASONS their names; 0 =
+    the message goes out and the cooldown entry moves to close_time[t]),
+    "detail": uint8 [S, T] (PT_D_* bits of a PT_CONTEXT_REJECTED candle), and
+    the `columns` of PT_VALUES, float64 [S, T], NaN where the method did not
+    reach them}. regime_routing only sets the message's autotrade flag
+    (price_tracker_routing); is_autotrade_suppressed reads the wall clock and
+    stays a host step, as do the message text and the dispatch."""
+    status, detail, vals = engine.price_tracker_replay(
+        c, rsi, macd, mfi, close_time, symbol_rs, ctx, ctx_ok, h=h, l=l, v=v, trend_score=trend_score,
+        state=state.tensors() if state is not None else None, first_t=first_t, lens=lens, from_t=from_t,
+        columns=columns, **params)
+    return {"status": status, "detail": detail, **vals}
+
+
+def _first_code(checks, none):
+    """The code (a float or an expression) beside the first true check."""
+    code = none if isinstance(none, F.Ex) else F.const(float(none))
+    for cond, value in reversed(checks):
+        code = F.where(cond, value if isinstance(value, F.Ex) else float(value), code)
+    return code
+
+
+# PriceTracker.regime_routing's strings (:113-163) as uint8 codes, in the method's order; the three f-string
+# families are expanded over their enums (market_regime_range / symbol_regime_range cannot occur)
+PT_ROUTE_REASONS = (("market_context_unavailable", "market_transitioning", "market_stress_too_high",
+                     "breadth_not_stable_for_mean_reversion", "market_regime_unavailable")
+                    + tuple(f"market_regime_{r.lower()}" for r in _lib.MARKET_REGIMES)
+                    + ("symbol_regime_unavailable", "symbol_transition_breakdown",
+                       "symbol_transition_volatility_expansion", "symbol_relative_strength_vs_btc_insufficient",
+                       "symbol_trend_score_outside_range", "symbol_range")
+                    + tuple(f"symbol_regime_{r.lower()}" for r in _lib.MICRO_REGIMES))
+PT_ROUTE_OK = PT_ROUTE_REASONS.index("symbol_range")
+
+
+def price_tracker_routing(context_ok, regime_is_transitioning, market_stress_score, advancers_ratio, long_tailwind,
+                          short_tailwind, market_regime, features_ok, micro_regime, micro_transition,
+                          relative_strength_vs_btc, trend_score, stress_threshold: float = 0.3,
+                          min_relative_strength: float = 0.005, max_abs_trend_score: float = 0.005):
+    """PriceTracker.regime_routing (strategies/coinrule/price_tracker.py:113-163,
+    with _has_stable_breadth :101-111) per (symbol, candle). The context's
+    fields [T] (or [S, T]): context_ok / regime_is_transitioning bool,
+    market_stress_score / advancers_ratio / long_tailwind / short_tailwind
+    float64, market_regime int8 (_lib.MARKET_REGIMES codes, negative: None);
+    the symbol's features [S, T]: features_ok bool (False: the context has
+    none for the symbol), micro_regime / micro_transition int8
+    (_lib.MICRO_REGIMES / MICRO_TRANSITIONS codes, negative: None),
+    relative_strength_vs_btc / trend_score float64 (the snapshot's, not the
+    frame's EMA score). stress_threshold: min(autotrade_stress_threshold, 0.3)
+    (:124). Returns (autotrade_ok bool [S, T], reason uint8 [S, T]): the first
+    refusing check in the method's order, PT_ROUTE_REASONS its strings
+    (PT_ROUTE_OK = "symbol_range", the accepting route). The verdict only
+    sets the emitted message's autotrade flag. One fused element-wise
+    program."""
+    S, T = trend_score.shape
+    R = PT_ROUTE_REASONS.index
+    STRESS, AR, LT, ST = (F.inp(x) for x in (market_stress_score, advancers_ratio, long_tailwind, short_tailwind))
+    MKT = F.inp(market_regime.to(torch.float64))
+    MR, MT = F.inp(micro_regime.to(torch.float64)), F.inp(micro_transition.to(torch.float64))
+    RS, TREND = F.inp(relative_strength_vs_btc), F.inp(trend_score)
+    stable = (AR >= 0.48) & (AR <= 0.62) & ((LT - ST).abs() <= 0.35)
+    rng_mkt, rng_sym = float(_lib.MARKET_REGIMES.index("RANGE")), float(_lib.MICRO_REGIMES.index("RANGE"))
+    code = _first_code([
+        (~F.inp(context_ok), R("market_context_unavailable")),
+        (F.inp(regime_is_transitioning), R("market_transitioning")),
+        (STRESS >= float(stress_threshold), R("market_stress_too_high")),
+        (~stable, R("breadth_not_stable_for_mean_reversion")),
+        (MKT < 0.0, R("market_regime_unavailable")),
+        (MKT != rng_mkt, MKT + float(R("market_regime_" + _lib.MARKET_REGIMES[0].lower()))),
+        (~F.inp(features_ok), R("symbol_regime_unavailable")),
+        (MT == float(_lib.MICRO_TRANSITIONS.index("BREAKDOWN")), R("symbol_transition_breakdown")),
+        (MT == float(_lib.MICRO_TRANSITIONS.index("VOLATILITY_EXPANSION")),
+         R("symbol_transition_volatility_expansion")),
+        (RS <= min_relative_strength, R("symbol_relative_strength_vs_btc_insufficient")),
+        (TREND.abs() > max_abs_trend_score, R("symbol_trend_score_outside_range")),
+        (MR == rng_sym, PT_ROUTE_OK),
+        (MR < 0.0, R("symbol_regime_unavailable")),
+    ], MR + float(R("symbol_regime_" + _lib.MICRO_REGIMES[0].lower())))
+    reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
+    return reason == PT_ROUTE_OK, reason
+
+
+# allows_long_autotrade's outcomes (market_regime/regime_routing.py:47-75) as uint8 codes: 0 allows, then the first
+# refusing check in the function's order (it returns a bare bool: the names are this library's)
+LONG_AUTOTRADE_REASONS = ("long_autotrade_allowed", "market_context_unavailable", "market_transitioning",
+                          "market_regime_not_stable", "market_regime_blocked", "market_stress_too_high",
+                          "market_regime_not_long", "symbol_trend_down_without_recovery", "symbol_volatile",
+                          "symbol_regime_not_long")
+
+
+def long_autotrade_allows(context_ok, regime_is_transitioning, timestamp, regime_stable_since, market_regime,
+                          market_stress_score, features_ok, micro_regime, micro_transition,
+                          min_age_ms: int = 30 * 60 * 1000, max_market_stress: float = 0.35):
+    """allows_long_autotrade with is_regime_stable / regime_age_ms
+    (market_regime/regime_routing.py:22-75) per (symbol, candle). The
+    context's fields [T] (or [S, T]): context_ok / regime_is_transitioning
+    bool, timestamp / regime_stable_since int64 ms (regime_stable_since
+    negative: None), market_regime int8 (_lib.MARKET_REGIMES codes, negative:
+    None), market_stress_score float64; the symbol's features [S, T]:
+    features_ok bool (False: no symbol given or no features for it),
+    micro_regime / micro_transition int8 (negative: None). The regime's age
+    max(timestamp - regime_stable_since, 0) is formed in int64 before it
+    enters the program (exact in float64 below 2^53 ms). Returns (ok bool
+    [S, T], reason uint8 [S, T], LONG_AUTOTRADE_REASONS its strings; 0 =
+    allowed). One fused element-wise program."""
+    S, T = micro_regime.shape
+    age = (timestamp - regime_stable_since).clamp_min(0)
+    AGE = F.inp(torch.where(regime_stable_since < 0, torch.full_like(age, -1), age).to(torch.float64))
+    MKT, STRESS = F.inp(market_regime.to(torch.float64)), F.inp(market_stress_score)
+    MR, MT = F.inp(micro_regime.to(torch.float64)), F.inp(micro_transition.to(torch.float64))
+    mk, mi, tr = _lib.MARKET_REGIMES.index, _lib.MICRO_REGIMES.index, _lib.MICRO_TRANSITIONS.index
+    blocked = ((MKT == float(mk("HIGH_STRESS"))) | (MKT == float(mk("TREND_DOWN")))
+               | (MKT == float(mk("TRANSITIONAL"))))
+    mkt_long = (MKT == float(mk("TREND_UP"))) | (MKT == float(mk("RANGE")))
+    sym_long = ((MR == float(mi("TREND_UP"))) | (MR == float(mi("RANGE"))) | (MR == float(mi("TRANSITIONAL"))))
+    FOK = F.inp(features_ok)
+    code = _first_code([
+        (~F.inp(context_ok), 1), (F.inp(regime_is_transitioning), 2),
+        ((AGE < 0.0) | (AGE < float(min_age_ms)), 3),   # no anchor yet, or too young
+        (blocked, 4), (STRESS >= max_market_stress, 5),
+        (~FOK & ~mkt_long, 6), (~FOK, 0),
+        ((MR == float(mi("TREND_DOWN"))) & (MT != float(tr("RECOVERY"))), 7),
+        (MR == float(mi("TREND_DOWN")), 0),
+        (MR == float(mi("VOLATILE")), 8), (~sym_long, 9),
+    ], 0)
+    reason = F.run({"reason": code}, S, T)["reason"].to(torch.uint8)
+    return reason == 0, reason
+
+
+# activity_burst_entry's status codes: where ActivityBurstPump.signal() returned (:164-185), in the method's order
+(AB_EMIT, AB_NO_FRAME, AB_SHORT_FRAME, AB_ROUTE_REFUSED, AB_NOT_QUALIFIED) = range(5)
+AB_REASONS = {AB_EMIT: "emit", AB_NO_FRAME: "no_frame", AB_SHORT_FRAME: "frame_too_short",
+              AB_ROUTE_REFUSED: "long_autotrade_refused", AB_NOT_QUALIFIED: "not_qualified"}
+
+
+def activity_burst_entry(qualified, route_ok, ctx_ok, *, first_t=None, lens=None, min_rows: int = 21):
+    """ActivityBurstPump.signal() from its frame gate to the qualified_signal
+    test (strategies/activity_burst_pump.py:164-185) per (symbol, candle):
+    qualified [S, T] bool (activity_burst_features' qualified_signal; column t
+    = the frame ending at t), route_ok [S, T] (or [S, 1] / [T]) bool:
+    allows_long_autotrade (long_autotrade_allows), read only where a context
+    exists; ctx_ok [T] (or one element) bool: latest_market_context is not
+    None. The frame is df.iloc[first_t[s]:t + 1], t < lens[s]; min_rows =
+    lookback_window + 1. Returns {"status": uint8 [S, T] (AB_* codes, the
+    first return in the method's order; 0 = the message goes out),
+    "autotrade": bool [S, T], the emitted message's flag (a context exists)}.
+    One fused element-wise program."""
+    S, T = qualified.shape
+    dev = qualified.device
+    tcol = torch.arange(T, dtype=torch.float64, device=dev)
+    rows = lambda x, dflt: (torch.full((S, 1), float(dflt), dtype=torch.float64, device=dev) if x is None else
+                            torch.as_tensor(x).to(device=dev, dtype=torch.float64).reshape(S, 1))
+    FIRST, LEN, TT = F.inp(rows(first_t, 0)), F.inp(rows(lens, T)), F.inp(tcol)
+    CTX = F.inp(ctx_ok.reshape(-1) if ctx_ok.numel() == T else ctx_ok.reshape(1, 1))
+    code = _first_code([
+        ((TT < FIRST) | (TT >= LEN), AB_NO_FRAME), (TT + 1.0 - FIRST < float(min_rows), AB_SHORT_FRAME),
+        (CTX & ~F.inp(route_ok), AB_ROUTE_REFUSED), (~F.inp(qualified), AB_NOT_QUALIFIED)], AB_EMIT)
+    res = F.run({"status": code, "autotrade": (code == float(AB_EMIT)) & CTX}, S, T)
+    return {"status": res["status"].to(torch.uint8), "autotrade": res["autotrade"]}

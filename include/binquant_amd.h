@@ -53,6 +53,9 @@
  *                         (strategies/gradual_gainer_retest.py:222-308)
  *   bq_spike_fade_replay <- FailedSpikeFade.signal()'s pending-spike state machine
  *                         (strategies/failed_spike_fade.py:596-695)
+ *   bq_price_tracker_replay <- PriceTracker.signal(): the null gate, the oversold test,
+ *                         the context score's rejections and the entry cooldown
+ *                         (strategies/coinrule/price_tracker.py:83-99, :165-251)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -458,6 +461,104 @@ int bq_spike_fade_replay(const double* open, const double* high, const double* c
                          const bq_spike_fade_params* params, uint8_t* st_active, int64_t* st_open_time,
                          double* st_high, double* st_close, uint8_t* event, uint8_t* detail, uint8_t* bars,
                          int64_t ld_out, void* stream);
+
+/*
+ * PriceTracker.signal() replayed over a panel of 5m frames
+ * (strategies/coinrule/price_tracker.py:165-324): column t of row s is what
+ * signal() does on the message whose frame is df.iloc[first:t + 1], first =
+ * first_t[s] (NULL: 0), after the messages of all earlier candles of the row.
+ * Candles t = max(from_t[s], first) (from_t NULL: 0) .. lens[s] - 1 (NULL: T)
+ * are replayed.
+ * close / high / low / volume [S][ld_px], rsi / macd / mfi [S][ld_ind]: the
+ * frame's columns; mfi[s][t] is what Indicators.mfi(frame) returns for the
+ * frame ending at t (pybinbot's formulas stay outside). high / low / volume are
+ * read only by the tail(tail_rows).isnull() test; NULL: the caller knows the
+ * column holds no NaN. close_time [S][ld_ct] int64 ms. trend_score [S][ld_tr]
+ * or NULL: formed in the pass, (ema_fast - ema_slow) / |ema_slow| (0 where
+ * ema_slow == 0) of closes.ewm(span, adjust=False).mean() over the frame, with
+ * pandas' update for missing (NaN, +-inf) closes. symbol_rs: the
+ * relative_strength_vs_btc of the row's entry in the context snapshot (0.0
+ * where it has none, context_scoring.py:26-32), [S] (ld_rs == 0) or [S][ld_rs].
+ * ctx [4][ld_ctx]: the rows confidence, long_tailwind, btc_regime_score,
+ * market_stress_score of latest_market_context at the candle's message; ctx_T
+ * == 1: one context for every candle, ctx_T == T: one per candle. ctx_ok
+ * [ctx_T] bytes, 0 where latest_market_context is None (NULL: present). Both
+ * are device memory: a captured graph sees values updated in place.
+ *
+ * Per candle, in the method's order:
+ *   # condition                                          status            lines
+ *   1 t outside [max(from_t, first), lens)               NO_FRAME
+ *   2 t + 1 - first < min_history, or a NaN among the    NOT_READY         :174-181
+ *     last tail_rows rows (of the frame) of close, rsi,
+ *     macd, high, low, volume (+-inf is not null)
+ *   3 not (rsi < rsi_max and macd < macd_max and         NO_SETUP          :194
+ *     mfi < mfi_max); a NaN fails
+ *   4 ctx_ok == 0                                        NO_CONTEXT        :228
+ *   5 followthrough < min_followthrough (D_FOLLOWTHROUGH) CONTEXT_REJECTED :236-242
+ *     or risk > max_risk (D_RISK) or confidence <        detail: the bits
+ *     min_confidence (D_CONFIDENCE); confidence <= 0
+ *     takes _empty_score and so sets D_CONFIDENCE
+ *   6 the row has a last entry and                       COOLDOWN          :83-93, :244-250
+ *     0 <= close_time[t] - last < cooldown_ms
+ *   0 otherwise                                          EMIT              :95-99, :251
+ *                                                        last = close_time[t]
+ * local_score = 1 + max(0, (rsi_max - rsi) / rsi_max) w_rsi + max(0, (mfi_max
+ * - mfi) / mfi_max) w_mfi + min(|macd| macd_scale, 1) w_macd (:198-203); the
+ * context score is the LONG branch of RuleBasedMarketContextModel.evaluate
+ * with local_features = {"trend_score"} (context_scoring.py:22-85) and
+ * SignalContextScorer.adjust_score (signal_context_scorer.py:20-29), each in
+ * the reference's operation order: bit for bit the Python floats for a given
+ * trend_score. cooldown_ms == 0: strategy_cooldowns is None, the cooldown is
+ * never active and nothing is marked. regime_routing, quiet hours, the message
+ * text and the dispatch only shape the emitted message: the caller's.
+ *
+ * st_has / st_last [S]: the row's strategy_cooldowns entry (present, its
+ * close_time), read, then written in place (a captured graph carries it); both
+ * NULL: start without an entry, discard. status [S][ld_out] bytes (BQ_PT_*),
+ * detail [S][ld_out] bytes (NULL = skip), values: NULL or BQ_PT_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_PT_V_* order,
+ * NaN where the method did not reach them (status 1-3). params NULL:
+ * bq_price_tracker_default_params. BQ_EINVAL, before any launch, unless every
+ * ld >= T (ld_rs: or 0), ctx_T is 1 or T, ld_ctx >= ctx_T, the state pointers
+ * are both NULL or both set, the thresholds and weights are finite, rsi_max
+ * and mfi_max are not 0, min_history >= 1, 1 <= tail_rows <=
+ * BQ_PT_MAX_TAIL_ROWS, spans >= 1, cooldown_ms >= 0. S == 0 or T == 0: BQ_OK.
+ */
+#define BQ_PT_MAX_TAIL_ROWS 64
+#define BQ_PT_NVALUES 6
+typedef struct bq_price_tracker_params {
+  int32_t min_history;        /* 30 (:177) */
+  int32_t tail_rows;          /* 5 (:175) */
+  int32_t span_fast;          /* 9 (:204) */
+  int32_t span_slow;          /* 21 (:205) */
+  double rsi_max;             /* 30 */
+  double macd_max;            /* 0 */
+  double mfi_max;             /* 20 */
+  double w_rsi;               /* 0.35 */
+  double w_mfi;               /* 0.35 */
+  double w_macd;              /* 0.3 */
+  double macd_scale;          /* 100 */
+  double context_weight;      /* 0.35 (:59-63) */
+  double risk_weight;         /* 0.35 */
+  double support_weight;      /* 0.2 */
+  double min_followthrough;   /* -0.2 (:237) */
+  double max_risk;            /* 0.6 (:238) */
+  double min_confidence;      /* 0.5 (:239) */
+  int64_t cooldown_ms;        /* ENTRY_COOLDOWN_BARS 12 x DEFAULT_INTERVAL_MS 300000; 0: no cooldown */
+} bq_price_tracker_params;
+enum { BQ_PT_EMIT = 0, BQ_PT_NO_FRAME, BQ_PT_NOT_READY, BQ_PT_NO_SETUP, BQ_PT_NO_CONTEXT, BQ_PT_CONTEXT_REJECTED,
+       BQ_PT_COOLDOWN };
+enum { BQ_PT_D_FOLLOWTHROUGH = 1, BQ_PT_D_RISK = 2, BQ_PT_D_CONFIDENCE = 4 };
+enum { BQ_PT_V_LOCAL = 0, BQ_PT_V_TREND, BQ_PT_V_FOLLOWTHROUGH, BQ_PT_V_RISK, BQ_PT_V_SUPPORT, BQ_PT_V_ADJUSTED };
+void bq_price_tracker_default_params(bq_price_tracker_params* p);
+int bq_price_tracker_replay(const double* close, const double* high, const double* low, const double* volume,
+                            int64_t ld_px, const double* rsi, const double* macd, const double* mfi, int64_t ld_ind,
+                            const int64_t* close_time, int64_t ld_ct, const double* trend_score, int64_t ld_tr,
+                            const double* symbol_rs, int64_t ld_rs, const double* ctx, int64_t ld_ctx,
+                            const uint8_t* ctx_ok, int64_t ctx_T, const int64_t* lens, const int64_t* first_t,
+                            const int64_t* from_t, int64_t S, int64_t T, const bq_price_tracker_params* params,
+                            uint8_t* st_has, int64_t* st_last, uint8_t* status, uint8_t* detail,
+                            double* const* values, int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t

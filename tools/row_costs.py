@@ -39,6 +39,19 @@ def sweep_cross():
     return _pump["score_cross"]
 
 
+_pt: dict = {}
+
+
+def price_tracker_cols():
+    """PriceTracker's columns, computed once: the enrichment's rsi / macd / mfi, a zero relative strength and one
+    context for every candle."""
+    if not _pt:
+        e = engine.enrich(o, h, l, c, v, columns=("rsi", "macd", "mfi"))
+        _pt.update(args=(c, e["rsi"], e["macd"], e["mfi"], ts + 899_999, torch.zeros(S, dtype=torch.float64, device="cuda"),
+                         torch.tensor([[0.9], [0.4], [0.3], [0.1]], dtype=torch.float64, device="cuda")))
+    return _pt["args"]
+
+
 def timeit(fn, reps=3):
     fn()
     torch.cuda.synchronize()
@@ -76,6 +89,8 @@ rows = {
     "spike_fade_replay": lambda: engine.spike_fade_replay(o, h, c, ts, spike_src),
     # LiquidationSweepPump's gate and the cohort winner per candle: the kernel alone over the pump columns, all outputs
     "sweep_select": lambda: engine.sweep_select(sweep_cols(), sweep_cross()),
+    # PriceTracker.signal()'s decisions, every output column, the EMA 9 / 21 formed in the pass
+    "price_tracker_entry": lambda: signals.price_tracker_entry(*price_tracker_cols(), h=h, l=l, v=v),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
