@@ -253,6 +253,32 @@ PT_CTX_ROWS = ("confidence", "long_tailwind", "btc_regime_score", "market_stress
 MARKET_REGIMES = ("TREND_UP", "TREND_DOWN", "RANGE", "HIGH_STRESS", "TRANSITIONAL")
 
 
+class BqMeanReversionParams(ctypes.Structure):
+    """Mirror of ``bq_mean_reversion_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("rsi_window", ctypes.c_int32), ("volume_ma_window", ctypes.c_int32), ("atr_ma_window", ctypes.c_int32),
+                ("ema_fast", ctypes.c_int32), ("ema_slow", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("rsi_short_min", ctypes.c_double), ("volume_ratio_min", ctypes.c_double),
+                ("atr_spike_max", ctypes.c_double), ("atr_stop_mult", ctypes.c_double),
+                ("max_entry_stop_loss_pct", ctypes.c_double), ("max_trend_score", ctypes.c_double),
+                ("max_market_stress", ctypes.c_double), ("max_gap", ctypes.c_double),
+                ("max_symbol_atr_pct", ctypes.c_double), ("min_wick_ratio", ctypes.c_double)]
+
+
+# bq_mean_reversion_replay: status codes (BQ_MR_*, the index is the code; 2-16 are the reference's own log reasons),
+# the value columns' order (the first MR_NFEATURES are the optional given features), the context rows' order, the
+# code of a None micro_regime / micro_regime_transition (the others: indices into MICRO_REGIMES / MICRO_TRANSITIONS)
+MR_MAX_WINDOW = 64
+MR_REASONS = ("emit", "no_frame", "indicators_not_ready", "atr_volatility_spike", "volume_below_average",
+              "invalid_candle_range", "no_fade_setup", "trend_score_above_max", "market_context_unavailable",
+              "market_stress_too_high", "symbol_atr_too_high", "market_context_long_edge", "btc_context_up",
+              "symbol_breakout_up", "symbol_trend_up", "candle_already_emitted", "entry_stop_loss_too_wide")
+MR_VALUES = ("rsi", "previous_rsi", "volume_ma", "atr_ma", "trend_score", "stop_loss_pct", "score")
+MR_NFEATURES = 5
+MR_CTX_ROWS = ("market_stress_score", "long_regime_score", "short_regime_score", "btc_regime_score", "btc_return")
+MR_NONE = 255
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -367,6 +393,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_price_tracker_replay": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64,
                                                _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64,
                                                ctypes.POINTER(BqPriceTrackerParams), _P, _P, _P, _P, _PP, _I64, _P]),
+    "bq_mean_reversion_default_params": (None, [ctypes.POINTER(BqMeanReversionParams)]),
+    "bq_mean_reversion_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _PP, _I64, _P,
+                                                _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                                ctypes.POINTER(BqMeanReversionParams), _P, _P, _P, _PP, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

@@ -1979,6 +1979,136 @@ def price_tracker_replay(c: torch.Tensor, rsi: torch.Tensor, macd: torch.Tensor,
     return status, det, outs
 
 
+MEAN_REVERSION_DEFAULTS = dict(   # MeanReversionFade's class attributes (strategies/mean_reversion_fade.py:52-73)
+    rsi_window=14, volume_ma_window=20, atr_ma_window=20, ema_fast=20, ema_slow=50, rsi_short_min=76.0,
+    volume_ratio_min=0.8, atr_spike_max=2.2, atr_stop_mult=2.0, max_entry_stop_loss_pct=1.5, max_trend_score=0.005,
+    max_market_stress=0.25, max_gap=0.02, max_symbol_atr_pct=0.03, min_wick_ratio=0.0)
+_MR_INT_PARAMS = ("rsi_window", "volume_ma_window", "atr_ma_window", "ema_fast", "ema_slow")
+_MR_SYM = (("ok", (torch.uint8, torch.bool)), ("atr_pct", (torch.float64,)), ("trend_score", (torch.float64,)),
+           ("regime", (torch.uint8,)), ("transition", (torch.uint8,)))
+
+
+@device_entry
+def mean_reversion_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Tensor, v: torch.Tensor,
+                          atr: torch.Tensor, bb_upper: torch.Tensor, open_time: torch.Tensor, ctx: torch.Tensor,
+                          ctx_ok: torch.Tensor | None = None, *, sym=None, features=None, state=None, first_t=None,
+                          lens=None, from_t=None, columns=_lib.MR_VALUES, **params):
+    """MeanReversionFade.signal() replayed over the panel
+    (strategies/mean_reversion_fade.py:224-300; bq_mean_reversion_replay):
+    column t of row s = the method on the message whose frame is
+    df_15m.iloc[first_t[s]:t + 1], after the messages of all earlier candles;
+    candles max(from_t[s], first_t[s]) .. lens[s] - 1 are replayed. o / h / l /
+    c / v / atr (the frame's ATR column) / bb_upper (the bb_high passed to
+    signal()) [S, T] float64 with unit stride along T and any row pitch;
+    open_time [S, T] int64, strictly ascending within a row's frame. ctx
+    float64 [5, Tc] (_lib.MR_CTX_ROWS), Tc 1 or T, and ctx_ok bool / uint8 [Tc]
+    (None: present), on the device. sym: None (no symbol has features in the
+    snapshot) or the (ok uint8 / bool, atr_pct float64, trend_score float64,
+    regime uint8, transition uint8) tensors, all [S] or all [S, T]; regime /
+    transition index _lib.MICRO_REGIMES / _lib.MICRO_TRANSITIONS, _lib.MR_NONE
+    for None. features: None (formed in the pass over the frame starting at
+    first_t) or the (rsi, previous_rsi, volume_ma, atr_ma, trend_score) [S, T]
+    float64 tensors. state: None (no entry, discard) or the (has uint8,
+    last_open_time int64) [S] tensors, updated in place. Returns (status uint8
+    [S, T] (_lib.MR_REASONS' indices), {name: float64 [S, T]} for `columns`, a
+    subset of _lib.MR_VALUES, NaN where the method did not reach them).
+    params: MEAN_REVERSION_DEFAULTS' keys."""
+    bad = set(params) - set(MEAN_REVERSION_DEFAULTS)
+    if bad:
+        raise ValueError(f"mean_reversion_replay: unknown parameters {sorted(bad)} "
+                         f"(known: {sorted(MEAN_REVERSION_DEFAULTS)})")
+    par = {**MEAN_REVERSION_DEFAULTS, **params}
+    for k, val in par.items():
+        if k not in _MR_INT_PARAMS and not math.isfinite(float(val)):
+            raise ValueError(f"mean_reversion_replay: {k} must be finite, got {val}")
+    if int(par["rsi_window"]) < 1 or int(par["ema_fast"]) < 1 or int(par["ema_slow"]) < 1:
+        raise ValueError("mean_reversion_replay: rsi_window and the spans must be >= 1")
+    if not all(1 <= int(par[k]) <= _lib.MR_MAX_WINDOW for k in ("volume_ma_window", "atr_ma_window")):
+        raise ValueError(f"mean_reversion_replay: volume_ma_window and atr_ma_window in 1..{_lib.MR_MAX_WINDOW}")
+    if float(par["rsi_short_min"]) == 100.0:
+        raise ValueError("mean_reversion_replay: 100 - rsi_short_min divides the score: not 100")
+    unknown = [k for k in columns if k not in _lib.MR_VALUES]
+    if unknown:
+        raise ValueError(f"mean_reversion_replay: unknown columns {unknown} (known: {_lib.MR_VALUES})")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    px = [(o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume")]
+    if features is not None:
+        if len(features) != _lib.MR_NFEATURES:
+            raise ValueError(f"features: expected {_lib.MR_VALUES[:_lib.MR_NFEATURES]}")
+        ft = list(zip(features, _lib.MR_VALUES))
+    else:
+        ft = []
+    for x, name in px + [(atr, "atr"), (bb_upper, "bb_upper")] + ft:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
+        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
+    nctx = len(_lib.MR_CTX_ROWS)
+    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
+            or ctx.shape[0] != nctx or ctx.shape[1] not in (1, T)):
+        raise ValueError(f"ctx: expected a float64 tensor of shape {(nctx, 1)} or {(nctx, T)} "
+                         f"(rows {_lib.MR_CTX_ROWS})")
+    Tc = int(ctx.shape[1])
+    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
+                               or tuple(ctx_ok.shape) != (Tc,)):
+        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
+    if sym is not None:
+        if len(sym) != len(_MR_SYM):
+            raise ValueError(f"sym: expected {tuple(n for n, _ in _MR_SYM)}")
+        shp = tuple(getattr(sym[0], "shape", ()))
+        if shp not in ((S,), (S, T)):
+            raise ValueError(f"sym: expected tensors of shape {(S,)} or {(S, T)}")
+        for x, (name, dts) in zip(sym, _MR_SYM):
+            if not isinstance(x, torch.Tensor) or x.dtype not in dts or tuple(x.shape) != shp:
+                raise ValueError(f"sym.{name}: expected a {dts[0]} tensor of shape {shp}")
+    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
+        _gate_rows(from_t, "from_t", S)
+    if state is not None:
+        if len(state) != 2:
+            raise ValueError("state: expected (has, last_open_time)")
+        for x, name, dt in zip(state, ("state.has", "state.last_open_time"), (torch.uint8, torch.int64)):
+            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
+                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    pxs, ld_px = _common_pitch([_check_panel(x, n) for x, n in px])
+    atr, bb_upper = _check_panel(atr, "atr"), _check_panel(bb_upper, "bb_upper")
+    fts, ld_ft = _common_pitch([_check_panel(x, n) for x, n in ft]) if ft else ([], T)
+    ot = _check_ts(open_time, "open_time")
+    others = [ctx] + ([ctx_ok] if ctx_ok is not None else []) + list(sym or ()) + list(state or ())
+    if not all(x.is_cuda for x in others):
+        raise ValueError("ctx / ctx_ok / sym / state: expected CUDA tensors (no CPU path)")
+    ld_sym = 0
+    if sym is not None:
+        sym = [x.contiguous() for x in sym]
+        ld_sym = T if sym[0].dim() == 2 else 0
+    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
+        ctx = ctx.contiguous()
+    ld_ctx = int(ctx.stride(0))
+    if ctx_ok is not None and not ctx_ok.is_contiguous():
+        ctx_ok = ctx_ok.contiguous()
+    dev = c.device
+    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    p = _lib.BqMeanReversionParams()
+    for k, val in par.items():
+        setattr(p, k, int(val) if k in _MR_INT_PARAMS else float(val))
+    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
+    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.MR_VALUES])
+    feats = _lib.ptr_array([x.data_ptr() for x in fts]) if fts else None
+    sh, sl = state if state is not None else (None, None)
+    sy = sym if sym is not None else [None] * len(_MR_SYM)
+    st = _lib.load().bq_mean_reversion_replay(
+        _ptr(pxs[0]), _ptr(pxs[1]), _ptr(pxs[2]), _ptr(pxs[3]), _ptr(pxs[4]), ld_px, _ptr(atr), _row_stride(atr),
+        _ptr(bb_upper), _row_stride(bb_upper), _ptr(ot), T, feats, ld_ft, _ptr(ctx), ld_ctx, _ptr(ctx_ok), Tc,
+        _ptr(sy[0]), _ptr(sy[1]), _ptr(sy[2]), _ptr(sy[3]), _ptr(sy[4]), ld_sym, _ptr(lens), _ptr(first_t),
+        _ptr(from_t), S, T, ctypes.byref(p), _ptr(sh), _ptr(sl), _ptr(status), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_mean_reversion_replay")
+    return status, outs
+
+
 def _join_capacity(ts: torch.Tensor, lens: torch.Tensor | None, bts: torch.Tensor) -> int:
     """Largest per-row count of (candle, benchmark row) matches over the
     candles t >= 1 that join (bench_ts ascending): an upper bound on every

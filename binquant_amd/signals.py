@@ -17,6 +17,12 @@ prefix frame df.iloc[:t + 1]:
 * top_gainer_features TopGainerEarlyMomentum._features
                      (strategies/top_gainer_early_momentum.py:92-160)
 * mean_reversion_features  the entry inputs of MeanReversionFade (:240-255)
+* mean_reversion_fade_entry  the decisions of MeanReversionFade.signal()
+                     (strategies/mean_reversion_fade.py:224-300) on the 15m
+                     frame: RSI hook and rolling means formed in the pass,
+                     _resolve_entry, the trend ceiling, the SHORT risk
+                     profile, once per candle, the stop-loss cap, one pass
+                     (bq_meanrev.hip)
 * impulse_rider_features   RelativeStrengthImpulseRider._features
                      (strategies/relative_strength_impulse_rider.py:92-198), one
                      pass (bq_impulse.hip)
@@ -753,6 +759,83 @@ def mean_reversion_features(o, h, l, c, v, atr, rsi_window: int = 14, volume_ma_
     })
     return {"rsi": res["rsi"], "previous_rsi": res["previous_rsi"], "volume_ma": vma, "atr_ma": ama,
             "trend_score": res["trend_score"], "upper_rejection_ratio": res["upper_rejection_ratio"]}
+
+
+# bq_mean_reversion_replay's status codes: where MeanReversionFade.signal() returned, in the method's order
+# (MR_REASONS: the method's own log reasons; "emit" and "no_frame" are this library's)
+MR_EMIT, MR_NO_FRAME, MR_NOT_READY = range(3)
+MR_REASONS = dict(enumerate(_lib.MR_REASONS))
+MR_VALUES = _lib.MR_VALUES
+MR_FEATURES = _lib.MR_VALUES[:_lib.MR_NFEATURES]
+MR_CTX_ROWS = _lib.MR_CTX_ROWS
+MR_SYM_KEYS = ("ok", "atr_pct", "trend_score", "micro_regime", "micro_transition")
+
+
+class MeanReversionState:
+    """MeanReversionFade's entries of strategy_cooldowns for S rows: has uint8
+    (the (ALGO, symbol) key is present) and last_open_time int64 (the open
+    time of the last emitted candle), each [S] on the device.
+    signals.mean_reversion_fade_entry / engine.mean_reversion_replay update it
+    in place, so a captured graph carries it from one message to the next."""
+
+    __slots__ = ("has", "last_open_time")
+
+    def __init__(self, has: torch.Tensor, last_open_time: torch.Tensor):
+        self.has, self.last_open_time = has, last_open_time
+
+    @classmethod
+    def empty(cls, S: int, device) -> "MeanReversionState":
+        return cls(torch.zeros(S, dtype=torch.uint8, device=device), torch.zeros(S, dtype=torch.int64, device=device))
+
+    def clone(self) -> "MeanReversionState":
+        return MeanReversionState(self.has.clone(), self.last_open_time.clone())
+
+    def tensors(self) -> tuple[torch.Tensor, torch.Tensor]:
+        return self.has, self.last_open_time
+
+
+def mean_reversion_fade_entry(o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_ok=None, *, sym=None, features=None,
+                              state: MeanReversionState | None = None, first_t=None, lens=None, from_t=None,
+                              columns=MR_VALUES, **params):
+    """The decisions of MeanReversionFade.signal() (strategies/mean_reversion_fade.py
+    :224-300) for every candle of a 15m panel in one pass
+    (engine.mean_reversion_replay, bq_mean_reversion_replay). Column t of row
+    s = the method on the message whose frame is df_15m.iloc[first_t[s]:t + 1],
+    after the messages of all earlier candles; candles from_t[s] .. lens[s] - 1
+    are replayed, from `state` (None: no candle emitted yet), which is updated
+    in place. o / h / l / c / v / atr / bb_upper [S, T] float64 (the enriched
+    frame's columns; bb_upper as the caller rounds it), open_time [S, T] int64
+    ms. ctx [5, 1] or [5, T] float64 (MR_CTX_ROWS) and ctx_ok [1] / [T]
+    (False: latest_market_context is None), both on the device. sym: None (no
+    symbol has features in the snapshot) or {MR_SYM_KEYS: tensor}, all [S] or
+    all [S, T]: ok (False: resolve_symbol_features gave None), atr_pct,
+    trend_score, micro_regime / micro_transition as uint8 indices into
+    _lib.MICRO_REGIMES / _lib.MICRO_TRANSITIONS (_lib.MR_NONE: None).
+    features: None to form rsi, previous_rsi, volume_ma, atr_ma and
+    trend_score in the pass (1e-9 of pandas), or mean_reversion_features'
+    dictionary. params: engine.MEAN_REVERSION_DEFAULTS' keys.
+
+    Returns {"status": uint8 [S, T] (MR_REASONS; 0 = the message goes out and
+    the row's state moves to open_time[t]), and the `columns` of MR_VALUES,
+    float64 [S, T], NaN where the method did not reach them}. stop_loss_pct
+    and score are unrounded: round_numbers(.., 4) / round(.., 4), the FUTURES
+    and ATR-column checks, the message text and the dispatch stay host
+    steps."""
+    if sym is not None:
+        missing = [k for k in MR_SYM_KEYS if k not in sym]
+        if missing:
+            raise ValueError(f"sym: missing {missing} (expected {MR_SYM_KEYS})")
+        sym = tuple(sym[k] for k in MR_SYM_KEYS)
+    if features is not None:
+        missing = [k for k in MR_FEATURES if k not in features]
+        if missing:
+            raise ValueError(f"features: missing {missing} (expected {MR_FEATURES})")
+        features = tuple(features[k] for k in MR_FEATURES)
+    status, vals = engine.mean_reversion_replay(
+        o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_ok, sym=sym, features=features,
+        state=state.tensors() if state is not None else None, first_t=first_t, lens=lens, from_t=from_t,
+        columns=columns, **params)
+    return {"status": status, **vals}
 
 
 # ---- the 5m strategies: PriceTracker and ActivityBurstPump --------------------------------------------------------

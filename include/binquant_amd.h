@@ -56,6 +56,10 @@
  *   bq_price_tracker_replay <- PriceTracker.signal(): the null gate, the oversold test,
  *                         the context score's rejections and the entry cooldown
  *                         (strategies/coinrule/price_tracker.py:83-99, :165-251)
+ *   bq_mean_reversion_replay <- MeanReversionFade.signal(): the Wilder RSI hook, the
+ *                         rolling means, _resolve_entry, the trend ceiling, the SHORT
+ *                         risk profile, the once-per-candle test and the stop-loss cap
+ *                         (strategies/mean_reversion_fade.py:88-212, :224-300)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -559,6 +563,136 @@ int bq_price_tracker_replay(const double* close, const double* high, const doubl
                             const int64_t* from_t, int64_t S, int64_t T, const bq_price_tracker_params* params,
                             uint8_t* st_has, int64_t* st_last, uint8_t* status, uint8_t* detail,
                             double* const* values, int64_t ld_out, void* stream);
+
+/*
+ * MeanReversionFade.signal() replayed over a panel of 15m frames
+ * (strategies/mean_reversion_fade.py:224-300, with _rsi :88-109, _resolve_entry
+ * :111-147, _trend_score :149-155, _stop_loss_pct :163-167, _score :157-161 and
+ * the SHORT branch of _risk_profile_allows :170-212): column t of row s is what
+ * signal() does on the message whose frame is df_15m.iloc[first:t + 1], first =
+ * first_t[s] (NULL: 0), after the messages of all earlier candles of the row.
+ * Candles t = max(from_t[s], first) (from_t NULL: 0) .. lens[s] - 1 (NULL: T)
+ * are replayed.
+ * open / high / low / close / volume [S][ld_px], atr [S][ld_atr] (the enriched
+ * frame's ATR column), bb_upper [S][ld_bb] (the bb_high the caller passes; its
+ * round_numbers(.., 6) stays with the caller), open_time [S][ld_ot] int64.
+ * features: NULL, or BQ_MR_NFEATURES host pointers to [S][ld_ft] doubles in
+ * BQ_MR_V_RSI .. BQ_MR_V_TREND order (all set): the method's own rsi,
+ * previous_rsi, volume_ma, atr_ma, trend_score, and the pass is point-wise.
+ * NULL: they are formed in the pass over the frame starting at first:
+ *   rsi          100 g / (g + l), 50.0 where g + l == 0, g / l the ewm(alpha =
+ *                1 / rsi_window, min_periods = rsi_window, adjust=False) means
+ *                of diff().clip(lower=0) / -diff().clip(upper=0)
+ *   previous_rsi rsi of candle t - 1 (NaN at t == first)
+ *   trend_score  (ema_fast - ema_slow) / |ema_slow| of ewm(span, adjust=False),
+ *                0.0 where ema_slow == 0
+ *   volume_ma,   rolling(window).mean() of volume / atr: NaN while the window
+ *   atr_ma       reaches before first or holds a missing value
+ * with pandas' update for missing (NaN, +-inf) closes. Domain: volume and atr
+ * finite or NaN inside the frame (+-inf there is outside the tested domain: the
+ * windows treat it as missing, as pandas does).
+ * ctx [5][ld_ctx]: the rows market_stress_score, long_regime_score,
+ * short_regime_score, btc_regime_score, btc_return of latest_market_context at
+ * the candle's message; ctx_T == 1: one context for every candle, ctx_T == T:
+ * one per candle. ctx_ok [ctx_T] bytes, 0 where the context is None (NULL:
+ * present). The symbol's entry in the context snapshot
+ * (resolve_symbol_features): sym_ok bytes (0: None; NULL: no symbol has one, the
+ * other four are not read), sym_atr_pct / sym_trend_score doubles, sym_regime /
+ * sym_transition bytes (BQ_MR_REGIME_* / BQ_MR_TRANSITION_*, the indices of the
+ * micro_regime / micro_regime_transition literals; BQ_MR_NONE for None); each
+ * [S] (ld_sym == 0) or [S][ld_sym]. All device memory.
+ *
+ * Per candle, in the method's order (a NaN fails a comparison as in Python):
+ *   #  condition                                               status
+ *   1  t outside [max(from_t, first), lens)                    NO_FRAME
+ *   2  rsi, previous_rsi, volume_ma, atr, atr_ma or            NOT_READY           :252-257
+ *      trend_score not finite (a one-row frame, where the
+ *      method itself raises IndexError at :245, is this)
+ *   3  atr >= atr_spike_max atr_ma                             ATR_SPIKE           :126
+ *   4  volume < volume_ratio_min volume_ma                     LOW_VOLUME          :128
+ *   5  high - low <= 0                                         BAD_RANGE           :131-133
+ *   6  not (rsi >= rsi_short_min and rsi < previous_rsi and    NO_SETUP            :135-147
+ *      close >= bb_upper and close < open and (high -
+ *      max(open, close)) / (high - low) >= min_wick_ratio)
+ *   7  trend_score > max_trend_score                           TREND_TOO_HIGH      :275
+ *   8  ctx_ok == 0                                             NO_CONTEXT          :177
+ *   9  market_stress_score >= max_market_stress                STRESS              :179
+ *   10 sym_ok and sym_atr_pct > max_symbol_atr_pct             SYMBOL_ATR          :182
+ *   11 long_regime_score > short_regime_score + max_gap        LONG_EDGE           :200-204
+ *   12 btc_regime_score > 0.15 and btc_return > 0              BTC_UP              :205
+ *   13 sym_ok and sym_transition == BREAKOUT_UP                BREAKOUT_UP         :208
+ *   14 sym_ok and sym_regime == TREND_UP and                   SYMBOL_TREND_UP     :210
+ *      sym_trend_score > 0
+ *   15 the row's last emitted candle is open_time[t]           ALREADY_EMITTED     :291
+ *   16 stop_loss_pct > max_entry_stop_loss_pct                 STOP_TOO_WIDE       :297
+ *   0  otherwise                                               EMIT                :300
+ *                                                              last = open_time[t]
+ * stop_loss_pct = min(max(atr_stop_mult atr / close 100, 0), 101), 0.0 where
+ * close <= 0 (the entry price is the candle's close); score = 1 + max(0, (rsi -
+ * rsi_short_min) / (100 - rsi_short_min)); both unrounded: round_numbers(.., 4)
+ * and round(.., 4) stay with the caller, as do the FUTURES check, the missing
+ * ATR column check, the message and the dispatch. _resolve_entry only ever
+ * returns Position.short, so the LONG branch of _risk_profile_allows
+ * (:185-198) cannot be reached and is not built.
+ *
+ * st_has / st_last [S]: the row's strategy_cooldowns entry (present, the open
+ * time of the last emitted candle), read, then written in place; both NULL:
+ * start without an entry, discard. Domain: open_time strictly ascending within
+ * [first, lens). The entry can equal open_time[t] only while it is still the
+ * one the call started with (an emit of an earlier candle moves it to a
+ * smaller time), so the test is a point-wise compare against the entry state
+ * plus "no candle of this call emitted before t", and the state after the call
+ * is the open time of the last emitting candle: no serial walk.
+ * status [S][ld_out] bytes (BQ_MR_*), values: NULL or BQ_MR_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_MR_V_* order,
+ * NaN where the method did not reach them: the five features on every replayed
+ * candle, stop_loss_pct on STOP_TOO_WIDE and EMIT, score on EMIT. params NULL:
+ * bq_mean_reversion_default_params. BQ_EINVAL, before any launch, unless every
+ * ld >= T (ld_sym: or 0), ctx_T is 1 or T, ld_ctx >= ctx_T, the features are
+ * all set or the table is NULL, the state pointers are both NULL or both set,
+ * the thresholds are finite, rsi_short_min != 100, rsi_window >= 1, the spans
+ * >= 1 and 1 <= volume_ma_window, atr_ma_window <= BQ_MR_MAX_WINDOW. S == 0 or
+ * T == 0: BQ_OK.
+ */
+#define BQ_MR_MAX_WINDOW 64
+#define BQ_MR_NVALUES 7
+#define BQ_MR_NFEATURES 5
+#define BQ_MR_NONE 255
+#define BQ_MR_REGIME_TREND_UP 0         /* micro_regime "TREND_UP" */
+#define BQ_MR_TRANSITION_BREAKOUT_UP 1  /* micro_regime_transition "BREAKOUT_UP" */
+typedef struct bq_mean_reversion_params {
+  int32_t rsi_window;                /* 14  RSI_WINDOW */
+  int32_t volume_ma_window;          /* 20  VOLUME_MA_WINDOW */
+  int32_t atr_ma_window;             /* 20  ATR_MA_WINDOW */
+  int32_t ema_fast;                  /* 20  EMA_FAST_WINDOW */
+  int32_t ema_slow;                  /* 50  EMA_SLOW_WINDOW */
+  int32_t reserved;                  /* 0 */
+  double rsi_short_min;              /* 76  RSI_SHORT_MIN */
+  double volume_ratio_min;           /* 0.8 VOLUME_RATIO_MIN */
+  double atr_spike_max;              /* 2.2 ATR_SPIKE_MAX */
+  double atr_stop_mult;              /* 2.0 ATR_STOP_MULT */
+  double max_entry_stop_loss_pct;    /* 1.5 MAX_ENTRY_STOP_LOSS_PCT */
+  double max_trend_score;            /* 0.005 MAX_TREND_SCORE */
+  double max_market_stress;          /* 0.25 MAX_MARKET_STRESS_SCORE */
+  double max_gap;                    /* 0.02 MAX_CONTEXT_COUNTER_TREND_GAP */
+  double max_symbol_atr_pct;         /* 0.03 MAX_SYMBOL_ATR_PCT */
+  double min_wick_ratio;             /* 0.0 MIN_REJECTION_WICK_RATIO */
+} bq_mean_reversion_params;
+enum { BQ_MR_EMIT = 0, BQ_MR_NO_FRAME, BQ_MR_NOT_READY, BQ_MR_ATR_SPIKE, BQ_MR_LOW_VOLUME, BQ_MR_BAD_RANGE,
+       BQ_MR_NO_SETUP, BQ_MR_TREND_TOO_HIGH, BQ_MR_NO_CONTEXT, BQ_MR_STRESS, BQ_MR_SYMBOL_ATR, BQ_MR_LONG_EDGE,
+       BQ_MR_BTC_UP, BQ_MR_BREAKOUT_UP, BQ_MR_SYMBOL_TREND_UP, BQ_MR_ALREADY_EMITTED, BQ_MR_STOP_TOO_WIDE };
+enum { BQ_MR_V_RSI = 0, BQ_MR_V_PREVIOUS_RSI, BQ_MR_V_VOLUME_MA, BQ_MR_V_ATR_MA, BQ_MR_V_TREND, BQ_MR_V_STOP_LOSS,
+       BQ_MR_V_SCORE };
+void bq_mean_reversion_default_params(bq_mean_reversion_params* p);
+int bq_mean_reversion_replay(const double* open, const double* high, const double* low, const double* close,
+                             const double* volume, int64_t ld_px, const double* atr, int64_t ld_atr,
+                             const double* bb_upper, int64_t ld_bb, const int64_t* open_time, int64_t ld_ot,
+                             const double* const* features, int64_t ld_ft, const double* ctx, int64_t ld_ctx,
+                             const uint8_t* ctx_ok, int64_t ctx_T, const uint8_t* sym_ok, const double* sym_atr_pct,
+                             const double* sym_trend_score, const uint8_t* sym_regime, const uint8_t* sym_transition,
+                             int64_t ld_sym, const int64_t* lens, const int64_t* first_t, const int64_t* from_t,
+                             int64_t S, int64_t T, const bq_mean_reversion_params* params, uint8_t* st_has,
+                             int64_t* st_last, uint8_t* status, double* const* values, int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t

@@ -91,6 +91,11 @@ rows = {
     "sweep_select": lambda: engine.sweep_select(sweep_cols(), sweep_cross()),
     # PriceTracker.signal()'s decisions, every output column, the EMA 9 / 21 formed in the pass
     "price_tracker_entry": lambda: signals.price_tracker_entry(*price_tracker_cols(), h=h, l=l, v=v),
+    # MeanReversionFade.signal()'s decisions, every output column, the RSI / means / trend score formed in the pass
+    # (bb_upper: the close as a stand-in column, one context for every candle, no snapshot)
+    "mean_reversion_fade_entry": lambda: signals.mean_reversion_fade_entry(
+        o, h, l, c, v, atr, c, ts, torch.tensor([[0.1], [0.2], [0.3], [0.0], [0.0]], dtype=torch.float64,
+                                                 device="cuda")),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
