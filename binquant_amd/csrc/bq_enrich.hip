@@ -28,8 +28,9 @@
 //     y50) — macd's signal EMA makes that a 3x3 lower-triangular system —
 //     after which each lane replays its 4 candles with pandas' exact
 //     ewm(adjust=False) update, so per-element rounding follows pandas.
-// HBM traffic: every input byte read once (plus one 24-byte neighbour read per
-// lane and tile), every output byte written once.
+// HBM traffic: every input byte read once (plus the 24-byte neighbour candle,
+// per lane and tile, per wave and tile in the hot kernel), every output byte
+// written once.
 #include "bq_rowtile.h"
 #include "binquant_amd.h"
 
@@ -259,7 +260,11 @@ __device__ __forceinline__ void put2(gdouble* row, int t, int T, bool full, dbl2
 // [128, 256), so each store instruction writes one contiguous KiB (lanes
 // permuted within it). `vec` is wave-uniform (a kernel argument), so every
 // lane takes part in the swap; `full` (every candle of the tile in range)
-// drops the range checks.
+// drops the range checks. tile_line_base: the candle of register A's pair
+// (line_offset<4>) for the lane whose own first candle is tb: lane 32 + a ->
+// wave base + 4a + 2. The hot kernel's prefetch loads from the same offsets.
+__device__ __forceinline__ int tile_line_base(int tb) { return __lane_id() < 32 ? tb : tb - 126; }
+
 __device__ __forceinline__ void store4(double* __restrict__ row_, int tb, int T, bool vec, const double (&x)[EN_K],
                                        bool full = false) {
   gdouble* row = (gdouble*)row_;
@@ -278,8 +283,7 @@ __device__ __forceinline__ void store4(double* __restrict__ row_, int tb, int T,
         a.u[i] = r[0];
         b.u[i] = r[1];
       }
-      const int lane = __lane_id();
-      const int ta = lane < 32 ? tb : tb - 126;   // lane 32 + a: wave base + 4a + 2
+      const int ta = tile_line_base(tb);
       put2(row, ta, T, full, a.d);
       put2(row, ta + 128, T, full, b.d);
       return;
@@ -308,25 +312,13 @@ struct Tile {
   double ph, pl, pc;   // candle tb-1 (NaN before the series start)
 };
 
-#ifndef BQ_EN_LINELOAD
-#define BQ_EN_LINELOAD 0   // line-covering input loads (bq_device.h load_pieces): measured 0.5-1.6% slower here
-#endif
-
 __device__ __forceinline__ void load_tile(const EnrichArgs& A, int64_t row, int tb, bool vin, Tile& t) {
   const int T = A.T;
-  if (BQ_EN_LINELOAD && vin) {   // wave-uniform; exchanged into place at use (tile_arrived)
-    load_pieces<EN_K>(A.in[BQ_OPEN] + row, tb, T, t.o, 0.0);
-    load_pieces<EN_K>(A.in[BQ_HIGH] + row, tb, T, t.h, 0.0);
-    load_pieces<EN_K>(A.in[BQ_LOW] + row, tb, T, t.l, 0.0);
-    load_pieces<EN_K>(A.in[BQ_CLOSE] + row, tb, T, t.c, 0.0);
-    load_pieces<EN_K>(A.in[BQ_VOLUME] + row, tb, T, t.v, 0.0);
-  } else {
-    load_lane<EN_K, false>(A.in[BQ_OPEN] + row, tb, T, vin, t.o);
-    load_lane<EN_K, false>(A.in[BQ_HIGH] + row, tb, T, vin, t.h);
-    load_lane<EN_K, false>(A.in[BQ_LOW] + row, tb, T, vin, t.l);
-    load_lane<EN_K, false>(A.in[BQ_CLOSE] + row, tb, T, vin, t.c);
-    load_lane<EN_K, false>(A.in[BQ_VOLUME] + row, tb, T, vin, t.v);
-  }
+  load_lane<EN_K, false>(A.in[BQ_OPEN] + row, tb, T, vin, t.o);
+  load_lane<EN_K, false>(A.in[BQ_HIGH] + row, tb, T, vin, t.h);
+  load_lane<EN_K, false>(A.in[BQ_LOW] + row, tb, T, vin, t.l);
+  load_lane<EN_K, false>(A.in[BQ_CLOSE] + row, tb, T, vin, t.c);
+  load_lane<EN_K, false>(A.in[BQ_VOLUME] + row, tb, T, vin, t.v);
   if (tb >= 1 && tb <= T) {
     t.ph = A.in[BQ_HIGH][row + tb - 1];
     t.pl = A.in[BQ_LOW][row + tb - 1];
@@ -336,34 +328,43 @@ __device__ __forceinline__ void load_tile(const EnrichArgs& A, int64_t row, int 
   }
 }
 
-// the prefetched tile's pieces -> each lane's EN_K consecutive candles
-__device__ __forceinline__ void tile_arrived(bool vin, Tile& t) {
-  if (BQ_EN_LINELOAD && vin) {
-    line_unexchange_x<EN_K>(t.o);
-    line_unexchange_x<EN_K>(t.h);
-    line_unexchange_x<EN_K>(t.l);
-    line_unexchange_x<EN_K>(t.c);
-    line_unexchange_x<EN_K>(t.v);
-  }
-}
-
 // ---- the hot kernel's prefetch (enrich_kernel<.., HOT>) ------------------------
 // load_tile puts the vector loads and the element-wise tail loads of a field
 // on the two sides of a divergent branch; the wait-count pass follows control
 // flow, so it drains (vmcnt(0)) ahead of every field and, because the stores
 // sit behind branches too, at the loop latch. Here nothing is branched around:
-// every lane loads both of its 16-byte pairs from an in-row address (a pair
-// that would reach past T is moved back to end at T - 1, which may leave it
-// 8-byte aligned), the neighbour candle likewise, and the lanes whose candles
-// lie past T select their values where the tile is consumed
-// (tile_tail_select). Needs T >= 2 and tb >= 1; whole tiles are not altered.
+// every lane loads two 16-byte pairs from in-row addresses (a pair that would
+// reach past T is moved back to end at T - 1, which may leave it 8-byte
+// aligned), the neighbour candle likewise, and the pairs past T are replaced
+// where the tile is consumed (tile_tail_select). Needs T >= 2 and tb >= 1;
+// whole tiles are not altered.
+//
+// BQ_EN_HOTLINE: the pairs are loaded in line order, the mapping store4 stores
+// in: lane L takes the pairs at tl + 128 j, tl = tile_line_base(tb), so each
+// dwordx4 instruction reads one contiguous KiB (a lane's own two pairs cover
+// half of each of 16 lines per instruction, every line requested twice), and
+// hot_tile_arrived exchanges them back into the lane's 4 consecutive candles.
+// BQ_EN_WAVENB: lanes 1-63 take the neighbour candle from lane - 1's last
+// candle of the arrived tile; the three neighbour loads then read the wave
+// slice's candle - 1 on every lane (one line each), which lane 0 keeps.
+#ifndef BQ_EN_HOTLINE
+#define BQ_EN_HOTLINE 1   // headline 24.085 -> 24.066 ms (profiles/enrich_lineload_ab.txt)
+#endif
+#ifndef BQ_EN_WAVENB
+#define BQ_EN_WAVENB 1    // 24.066 -> 23.966 ms
+#endif
+#ifndef BQ_EN_TPDIV
+#define BQ_EN_TPDIV 0   // the tile body's typical price with the IEEE divide (same bits, ~9 more instructions each: 24.085 -> 24.226 ms)
+#endif
 typedef dbl2 __attribute__((aligned(8))) dbl2u;
+constexpr int EN_PS = BQ_EN_HOTLINE ? 128 : 2;   // candles between a lane's two prefetched pairs
 
-__device__ __forceinline__ void load_tile_clamped(const EnrichArgs& A, int64_t row, int tb, Tile& t) {
+// tp: candle of the lane's first pair (tile_line_base(tb), or tb itself without BQ_EN_HOTLINE)
+__device__ __forceinline__ void load_tile_clamped(const EnrichArgs& A, int64_t row, int tb, int tp, Tile& t) {
   const int T = A.T;
   int64_t u[EN_K / 2];
 #pragma unroll
-  for (int j = 0; j < EN_K / 2; ++j) u[j] = row + min(tb + 2 * j, T - 2);
+  for (int j = 0; j < EN_K / 2; ++j) u[j] = row + min(tp + EN_PS * j, T - 2);
   auto field = [&](const double* __restrict__ f, double (&x)[EN_K]) {
 #pragma unroll
     for (int j = 0; j < EN_K / 2; ++j) {
@@ -377,20 +378,24 @@ __device__ __forceinline__ void load_tile_clamped(const EnrichArgs& A, int64_t r
   field(A.in[BQ_LOW], t.l);
   field(A.in[BQ_CLOSE], t.c);
   field(A.in[BQ_VOLUME], t.v);
-  const int64_t n = row + min(tb - 1, T - 1);
+  // with BQ_EN_WAVENB the wave slice's neighbour: formed from the thread's
+  // index, so the loads stay vector loads (counted by vmcnt with the rest)
+  const int nb = BQ_EN_WAVENB ? tb - EN_K * (int)__lane_id() : tb;
+  const int64_t n = row + min(nb - 1, T - 1);
   t.ph = A.in[BQ_HIGH][n];
   t.pl = A.in[BQ_LOW][n];
   t.pc = A.in[BQ_CLOSE][n];
 }
 
 // the partial last tile as load_tile would have delivered it: candles past T
-// are 0.0, a lane whose block starts past T has no neighbour (NaN). A moved
-// pair holds candles T - 2, T - 1: candle T - 1 is its second element.
-__device__ __forceinline__ void tile_tail_select(int tb, int T, Tile& t) {
+// are 0.0. Pair by pair on the loading lane, ahead of the exchange, which
+// moves whole pairs. A moved pair holds candles T - 2, T - 1: candle T - 1 is
+// its second element.
+__device__ __forceinline__ void tile_tail_select(int tp, int T, Tile& t) {
   auto field = [&](double (&x)[EN_K]) {
 #pragma unroll
     for (int j = 0; j < EN_K / 2; ++j) {
-      const int u = tb + 2 * j;
+      const int u = tp + EN_PS * j;
       const bool both = u + 2 <= T, one = u < T;
       x[2 * j] = both ? x[2 * j] : (one ? x[2 * j + 1] : 0.0);
       x[2 * j + 1] = both ? x[2 * j + 1] : 0.0;
@@ -401,7 +406,37 @@ __device__ __forceinline__ void tile_tail_select(int tb, int T, Tile& t) {
   field(t.l);
   field(t.c);
   field(t.v);
-  if (tb > T) t.ph = t.pl = t.pc = qnan();
+}
+
+// x of lane - 1; lane 0 keeps `keep` (DPP's old operand: no select)
+__device__ __forceinline__ double prev_lane_or(double keep, double x) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(keep), __double2loint(x), DPP_WAVE_SHR1, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(keep), __double2hiint(x), DPP_WAVE_SHR1, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+
+// the prefetched tile where it is consumed: the pairs exchanged back into each
+// lane's EN_K consecutive candles (every lane takes part), the neighbour candle
+// from the lane before. TAIL: a partial tile; a lane whose block starts past
+// T has no neighbour (NaN).
+template <bool TAIL>
+__device__ __forceinline__ void hot_tile_arrived(int tb, int tp, int T, Tile& t) {
+  if constexpr (TAIL) tile_tail_select(tp, T, t);
+#if BQ_EN_HOTLINE
+  line_unexchange_x<EN_K>(t.o);
+  line_unexchange_x<EN_K>(t.h);
+  line_unexchange_x<EN_K>(t.l);
+  line_unexchange_x<EN_K>(t.c);
+  line_unexchange_x<EN_K>(t.v);
+#endif
+#if BQ_EN_WAVENB
+  t.ph = prev_lane_or(t.ph, t.h[EN_K - 1]);
+  t.pl = prev_lane_or(t.pl, t.l[EN_K - 1]);
+  t.pc = prev_lane_or(t.pc, t.c[EN_K - 1]);
+#endif
+  if constexpr (TAIL) {
+    if (tb > T) t.ph = t.pl = t.pc = qnan();
+  }
 }
 
 // how one instantiation of the tile body treats its tile. GEN: everything
@@ -576,7 +611,7 @@ __device__ __forceinline__ void enrich_row_missing(const EnrichArgs& P, const Em
 // for the prefetched tile stay counted across the tile's 28 stores.
 template <bool DIV, bool VOUT, bool DEF, bool HOT = false>
 __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichArgs A, int vec_in) {
-  static_assert(!HOT || (!DIV && VOUT && DEF && !BQ_EN_LINELOAD && EN_K == 4), "HOT: the common call only");
+  static_assert(!HOT || (!DIV && VOUT && DEF && EN_K == 4), "HOT: the common call only");
   // LDS ring (positions [0, H) = halo from the previous tile, [H, R) = tile)
   __shared__ double sP[EN_R];    // close prefix: halo re-based, tile wave-local
   __shared__ double sC[EN_R];    // close
@@ -644,7 +679,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
   // its first value (output[0] = x0, macd signal[0] = macd[0] = 0), and the
   // generic step from y == x leaves y unchanged, so no first-candle branch.
   if (tid == 0) {
-    const double x0 = nx.c[0];   // candle 0 in either load order (line_offset(0) == 0)
+    const double x0 = nx.c[0];
     sEcar[E_FAST] = sEcar[E_SLOW] = sEcar[E_0] = sEcar[E_1] = x0;
     sEcar[E_SIG] = 0.0;
   }
@@ -681,8 +716,11 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     const EnrichArgs& P = sA;
     auto has = [&](int col) { return HOT || P.out[col] != nullptr; };   // HOT: every column, no branch
     Tile cu = nx;
-    if constexpr (M::SEL) tile_tail_select(tb, T, cu);
-    else tile_arrived(vin, cu);
+    // the hot kernel's tiles behind tile 0 consume what load_tile_clamped
+    // prefetched; tile 0 and the generic kernels what load_tile delivered
+    constexpr bool ARRIVE = !M::GEN && !M::WARM;
+    const int tp = BQ_EN_HOTLINE ? tile_line_base(tb) : tb;
+    if constexpr (ARRIVE) hot_tile_arrived<M::SEL>(tb, tp, T, cu);
     if constexpr (M::GEN) {
       if (t0 + EN_TT < T) load_tile(A, irow, tb + EN_TT, vin, nx);   // prefetch tile n+1
     }
@@ -690,14 +728,22 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     // ---- phase 1: per-candle quantities into the LDS ring --------------------
     {
       bool miss = false;   // a missing / non-finite input among the lane's candles (enrich_row_missing)
+      // typical price (h + l + c) / 3 through div_exact: the IEEE quotient's
+      // bits for a finite sum (tests/test_div_exact.py) at 3 instructions for
+      // the divide's ~12; a non-finite one stays non-finite and flags the row
+#if BQ_EN_TPDIV
+      auto tprice = [](double h, double l, double c) { return typical_price(h, l, c); };
+#else
+      auto tprice = [](double h, double l, double c) { return div_exact((h + l) + c, 3.0, 1.0 / 3.0); };
+#endif
       double pc = cu.pc;
-      double tpp = typical_price(cu.ph, cu.pl, cu.pc);
+      double tpp = tprice(cu.ph, cu.pl, cu.pc);
       int run = -1;
 #pragma unroll
       for (int k = 0; k < EN_K; ++k) {
         const int t = tb + k;
         const double c = cu.c[k];
-        const double tp = typical_price(cu.h[k], cu.l[k], c);
+        const double tp = tprice(cu.h[k], cu.l[k], c);
         const double mf = tp * cu.v[k];
         const double o4 = ohlc4(cu.o[k], cu.h[k], cu.l[k], c);
         miss |= !__builtin_isfinite(o4) | !__builtin_isfinite(mf);   // any of o, h, l, c, v (or an overflow)
@@ -717,7 +763,7 @@ __global__ __launch_bounds__(EN_NT, BQ_EN_WPS) void enrich_kernel(const EnrichAr
     // so the two tiles' registers overlap in the closes only (issued at the
     // top of the tile, or behind the wave scans just ahead of B1, it measured
     // 0.5-0.9 ms slower at the headline)
-    if constexpr (M::PREF) load_tile_clamped(A, irow, tb + EN_TT, nx);
+    if constexpr (M::PREF) load_tile_clamped(A, irow, tb + EN_TT, tp + EN_TT, nx);
     // close prefix (compensated), wave-local
     {
       dd tot = {0.0, 0.0};
@@ -1269,11 +1315,11 @@ int bq_enrich(const double* const* in, int64_t S, int64_t T, int64_t ld_in, cons
   const bool def = P.ma_periods[0] == 7 && P.ma_periods[1] == 25 && P.ma_periods[2] == 100 && P.rsi_window == 14 &&
                    P.bb_window == 20 && P.atr_window == 14 && P.twap_window == 12 && P.mfi_window == 14;
   // the common call: every column, aligned rows, the reference's windows, integer spans
-  bool hot = def && !div && vout && vin && !BQ_EN_LINELOAD && EN_K == 4;
+  bool hot = def && !div && vout && vin && EN_K == 4;
   for (int i = 0; i < BQ_NUM_ENRICH_COLS; ++i) hot &= out[i] != nullptr;
 #define BQ_EN_LAUNCH(D, V, F) hipLaunchKernelGGL((enrich_kernel<D, V, F>), grid, block, 0, st, A, vin)
   if (hot) {
-    if constexpr (!BQ_EN_LINELOAD && EN_K == 4)
+    if constexpr (EN_K == 4)
       hipLaunchKernelGGL((enrich_kernel<false, true, true, true>), grid, block, 0, st, A, vin);
   } else if (def) {
     if (div && vout) BQ_EN_LAUNCH(true, true, true);

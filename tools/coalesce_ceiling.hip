@@ -213,13 +213,69 @@ __global__ __launch_bounds__(NT) void walk_swap(Args a) {
   }
 }
 
+// the kernel's read side as a whole: whole-line stores, half- or whole-line
+// (LSPLIT) tile loads, and the neighbour candle (candle - 1 of rows 1..3, the
+// kernel's high, low and close) that the other variants leave out. NB 1: per
+// lane, the candle ahead of the lane's own four (8 bytes at a 32-byte stride,
+// 16 lines per instruction, all of them lines the tile loads anyway); NB 2:
+// the candle ahead of the wave's slice on every lane (one line per
+// instruction); NB 0: none.
+template <bool LSPLIT, int NB>
+__global__ __launch_bounds__(NT) void walk_nb(Args a) {
+  extern __shared__ double occupancy_limiter[];
+  if (a.S < 0) occupancy_limiter[threadIdx.x] = 0.0;
+  const long base = (long)blockIdx.x * a.ld;
+  const int tid = threadIdx.x;
+  int la, lb, sa, sb;
+  offs<LSPLIT>(tid, la, lb);
+  offs<true>(tid, sa, sb);
+  const int nb = NB == 2 ? 4 * (tid & ~63) : 4 * tid;   // from the thread index: vector loads
+  dbl2 nx[NIN][2];
+  double np[3] = {0.0, 0.0, 0.0};
+  for (int f = 0; f < NIN; ++f) {
+    nx[f][0] = *reinterpret_cast<const dbl2*>(a.in[f] + base + la);
+    nx[f][1] = *reinterpret_cast<const dbl2*>(a.in[f] + base + lb);
+  }
+  for (long t0 = 0; t0 < a.T; t0 += TILE) {
+    dbl2 cu[NIN][2];
+    double cp[3];
+    for (int f = 0; f < NIN; ++f) {
+      cu[f][0] = nx[f][0];
+      cu[f][1] = nx[f][1];
+    }
+    for (int f = 0; f < 3; ++f) cp[f] = np[f];
+    if (t0 + TILE < a.T) {
+      for (int f = 0; f < NIN; ++f) {
+        nx[f][0] = *reinterpret_cast<const dbl2*>(a.in[f] + base + t0 + TILE + la);
+        nx[f][1] = *reinterpret_cast<const dbl2*>(a.in[f] + base + t0 + TILE + lb);
+      }
+      if (NB)
+        for (int f = 0; f < 3; ++f) np[f] = a.in[1 + f][base + t0 + TILE + nb - 1];   // t0 + TILE >= 1: in the row
+    }
+    dbl2 s0 = {0, 0}, s1 = {0, 0};
+    for (int f = 0; f < NIN; ++f) {
+      s0 += cu[f][0];
+      s1 += cu[f][1];
+    }
+    if (NB) s1 += (cp[0] + cp[1]) + cp[2];
+    for (int o = 0; o < NOUT; ++o) {
+      __builtin_nontemporal_store(s0 + (double)o, reinterpret_cast<dbl2*>(a.out[o] + base + t0 + sa));
+      __builtin_nontemporal_store(s1, reinterpret_cast<dbl2*>(a.out[o] + base + t0 + sb));
+    }
+  }
+}
+
 int main(int argc, char** argv) {
   const long S = argc > 1 ? atol(argv[1]) : 12500, T = 10240;   // whole tiles: the probe has no tail path
   const int reps = 10;
   struct V { const char* name; int split; int nts; int lds; };   // split 2/3: walk2<256>/<512>
   const bool quick = argc > 2;   // only the kernel-relevant variants
   const V vq[] = {{"half_nt_3wg", 0, 1, 52000}, {"split_nt_3wg", 1, 1, 52000}, {"swap_perm_3wg", 7, 1, 52000},
-                  {"swap_bperm_3wg", 8, 1, 52000}, {"half_nt_3wg_b", 0, 1, 52000}, {"swap_perm_3wg_b", 7, 1, 52000}};
+                  {"swap_bperm_3wg", 8, 1, 52000}, {"half_nt_3wg_b", 0, 1, 52000}, {"swap_perm_3wg_b", 7, 1, 52000},
+                  {"lhalf_sline_nb0", 9, 1, 52000}, {"lhalf_sline_nblane", 10, 1, 52000},
+                  {"lhalf_sline_nbwave", 11, 1, 52000}, {"lline_sline_nb0", 12, 1, 52000},
+                  {"lline_sline_nblane", 13, 1, 52000}, {"lline_sline_nbwave", 14, 1, 52000},
+                  {"lhalf_sline_nblane_b", 10, 1, 52000}, {"lline_sline_nbwave_b", 14, 1, 52000}};
   const V vs[] = {
       {"half_3wg", 0, 0, 52000}, {"split_3wg", 1, 0, 52000}, {"half_nt_3wg", 0, 1, 52000},
       {"split_nt_3wg", 1, 1, 52000}, {"half_nt_4wg", 0, 1, 39000}, {"split_nt_4wg", 1, 1, 39000},
@@ -229,6 +285,8 @@ int main(int argc, char** argv) {
       {"mix_lhalf_s4half", 4, 1, 52000}, {"mix_lhalf_s0half", 5, 1, 52000}, {"mix_lsplit_s4half", 6, 1, 52000},
       {"split_nt_3wg_c", 1, 1, 52000}, {"half_nt_3wg_c", 0, 1, 52000},
       {"swap_perm_3wg", 7, 1, 52000}, {"swap_bperm_3wg", 8, 1, 52000},
+      {"lhalf_sline_nb0", 9, 1, 52000}, {"lhalf_sline_nblane", 10, 1, 52000}, {"lhalf_sline_nbwave", 11, 1, 52000},
+      {"lline_sline_nb0", 12, 1, 52000}, {"lline_sline_nblane", 13, 1, 52000}, {"lline_sline_nbwave", 14, 1, 52000},
   };
   const size_t arr = (size_t)S * T * sizeof(double);
   char* buf;
@@ -250,6 +308,12 @@ int main(int argc, char** argv) {
       if (r == 2) CK(hipEventRecord(e0));
       if (v.split == 7) walk_swap<false><<<S, NT, v.lds>>>(a);
       else if (v.split == 8) walk_swap<true><<<S, NT, v.lds>>>(a);
+      else if (v.split == 9) walk_nb<false, 0><<<S, NT, v.lds>>>(a);
+      else if (v.split == 10) walk_nb<false, 1><<<S, NT, v.lds>>>(a);
+      else if (v.split == 11) walk_nb<false, 2><<<S, NT, v.lds>>>(a);
+      else if (v.split == 12) walk_nb<true, 0><<<S, NT, v.lds>>>(a);
+      else if (v.split == 13) walk_nb<true, 1><<<S, NT, v.lds>>>(a);
+      else if (v.split == 14) walk_nb<true, 2><<<S, NT, v.lds>>>(a);
       else if (v.split == 4) walk_mix<false, 4><<<S, NT, v.lds>>>(a);
       else if (v.split == 5) walk_mix<false, 0><<<S, NT, v.lds>>>(a);
       else if (v.split == 6) walk_mix<true, 4><<<S, NT, v.lds>>>(a);
