@@ -279,6 +279,32 @@ MR_CTX_ROWS = ("market_stress_score", "long_regime_score", "short_regime_score",
 MR_NONE = 255
 
 
+class BqRangeFadeParams(ctypes.Structure):
+    """Mirror of ``bq_range_fade_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("min_candles", ctypes.c_int32), ("adx_window", ctypes.c_int32), ("zscore_window", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("adx_max", ctypes.c_double), ("long_rsi_max", ctypes.c_double),
+                ("short_rsi_min", ctypes.c_double), ("long_zscore_max", ctypes.c_double),
+                ("short_zscore_min", ctypes.c_double), ("band_touch_tolerance", ctypes.c_double),
+                ("max_market_stress", ctypes.c_double), ("max_symbol_atr_pct", ctypes.c_double),
+                ("max_symbol_bb_width", ctypes.c_double), ("min_rejection_wick_frac", ctypes.c_double),
+                ("long_close_position_min", ctypes.c_double), ("short_close_position_max", ctypes.c_double)]
+
+
+# bq_range_fade_replay: status codes (BQ_RF_*, the index is the code; 2-14 are the points where
+# RangeBbRsiMeanReversion.signal() returns, regime_routing's reasons by their fixed part), the value columns' order
+# (the first RF_NFEATURES are the optional given features), the context rows' order (market_regime: an index into
+# MARKET_REGIMES, MR_NONE for None), the windows' limits
+RF_MAX_ADX_WINDOW, RF_MAX_ZSCORE_WINDOW = 32, 64
+RF_REASONS = ("emit", "no_frame", "not_enough_data", "market_context_unavailable", "market_transitioning",
+              "market_stress_too_high", "market_regime_unavailable", "market_regime_not_range",
+              "symbol_regime_unavailable", "symbol_regime_not_range", "symbol_transition", "symbol_atr_too_high",
+              "symbol_bb_width_too_high", "adx_too_high", "no_bb_rsi_rejection_setup")
+RF_VALUES = ("adx", "zscore", "direction", "score")
+RF_NFEATURES = 2
+RF_CTX_ROWS = ("regime_is_transitioning", "market_stress_score", "market_regime")
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -397,6 +423,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_mean_reversion_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _PP, _I64, _P,
                                                 _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                                 ctypes.POINTER(BqMeanReversionParams), _P, _P, _P, _PP, _I64, _P]),
+    "bq_range_fade_default_params": (None, [ctypes.POINTER(BqRangeFadeParams)]),
+    "bq_range_fade_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _PP, _I64, _P, _I64,
+                                            _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                            ctypes.POINTER(BqRangeFadeParams), _P, _PP, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

@@ -2109,6 +2109,131 @@ def mean_reversion_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: 
     return status, outs
 
 
+RANGE_FADE_DEFAULTS = dict(   # RangeBbRsiMeanReversion's class attributes (range_bb_rsi_mean_reversion.py:37-51)
+    min_candles=40, adx_window=14, zscore_window=20, adx_max=32.0, long_rsi_max=35.0, short_rsi_min=65.0,
+    long_zscore_max=-2.0, short_zscore_min=2.0, band_touch_tolerance=0.002, max_market_stress=0.35,
+    max_symbol_atr_pct=0.04, max_symbol_bb_width=0.08, min_rejection_wick_frac=0.30, long_close_position_min=0.55,
+    short_close_position_max=0.45)
+_RF_INT_PARAMS = ("min_candles", "adx_window", "zscore_window")
+_RF_SYM = (("ok", (torch.uint8, torch.bool)), ("micro_regime", (torch.uint8,)), ("micro_transition", (torch.uint8,)),
+           ("atr_pct", (torch.float64,)), ("bb_width", (torch.float64,)))
+
+
+@device_entry
+def range_fade_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Tensor, v: torch.Tensor,
+                      rsi: torch.Tensor, bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tensor,
+                      ctx: torch.Tensor, ctx_ok: torch.Tensor | None = None, *, sym=None, features=None, first_t=None,
+                      lens=None, from_t=None, columns=_lib.RF_VALUES, **params):
+    """RangeBbRsiMeanReversion.signal() replayed over the panel
+    (strategies/range_bb_rsi_mean_reversion.py:202-274; bq_range_fade_replay):
+    column t of row s = the method on the message whose frame is
+    df_15m.iloc[first_t[s]:t + 1]; candles max(from_t[s], first_t[s]) ..
+    lens[s] - 1 are replayed. The strategy keeps no cooldown entry: no state.
+    o / h / l / c / v / rsi (the enriched frame's columns; v only feeds the
+    null gate) / bb_upper / bb_mid / bb_lower (the bb_high, bb_mid, bb_low
+    passed to signal(), as the caller rounds them) [S, T] float64 with unit
+    stride along T and any row pitch; current_price is the candle's close. ctx
+    float64 [3, Tc] (_lib.RF_CTX_ROWS; market_regime an index into
+    _lib.MARKET_REGIMES, _lib.MR_NONE for None), Tc 1 or T, and ctx_ok bool /
+    uint8 [Tc] (None: present), on the device. sym: None (no symbol has
+    features in the snapshot) or the (ok uint8 / bool, micro_regime uint8,
+    micro_transition uint8, atr_pct float64, bb_width float64) tensors, all [S]
+    or all [S, T]; the codes index _lib.MICRO_REGIMES / _lib.MICRO_TRANSITIONS,
+    _lib.MR_NONE for None. features: None (adx and zscore are formed in the
+    pass over the frame starting at first_t) or the (adx, zscore) [S, T]
+    float64 tensors. Returns (status uint8 [S, T] (_lib.RF_REASONS' indices),
+    {name: float64 [S, T]} for `columns`, a subset of _lib.RF_VALUES, NaN where
+    the method did not reach them). params: RANGE_FADE_DEFAULTS' keys."""
+    bad = set(params) - set(RANGE_FADE_DEFAULTS)
+    if bad:
+        raise ValueError(f"range_fade_replay: unknown parameters {sorted(bad)} "
+                         f"(known: {sorted(RANGE_FADE_DEFAULTS)})")
+    par = {**RANGE_FADE_DEFAULTS, **params}
+    for k, val in par.items():
+        if k not in _RF_INT_PARAMS and not math.isfinite(float(val)):
+            raise ValueError(f"range_fade_replay: {k} must be finite, got {val}")
+    if int(par["min_candles"]) < 1:
+        raise ValueError("range_fade_replay: min_candles must be >= 1")
+    if not 1 <= int(par["adx_window"]) <= _lib.RF_MAX_ADX_WINDOW:
+        raise ValueError(f"range_fade_replay: adx_window in 1..{_lib.RF_MAX_ADX_WINDOW}")
+    if not 1 <= int(par["zscore_window"]) <= _lib.RF_MAX_ZSCORE_WINDOW:
+        raise ValueError(f"range_fade_replay: zscore_window in 1..{_lib.RF_MAX_ZSCORE_WINDOW}")
+    if float(par["adx_max"]) == 0.0 or float(par["long_rsi_max"]) == 0.0:
+        raise ValueError("range_fade_replay: adx_max and long_rsi_max divide the score: not 0")
+    unknown = [k for k in columns if k not in _lib.RF_VALUES]
+    if unknown:
+        raise ValueError(f"range_fade_replay: unknown columns {unknown} (known: {_lib.RF_VALUES})")
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    S, T = c.shape
+    px = [(o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume")]
+    bb = [(bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower")]
+    if features is not None:
+        if len(features) != _lib.RF_NFEATURES:
+            raise ValueError(f"features: expected {_lib.RF_VALUES[:_lib.RF_NFEATURES]}")
+        ft = list(zip(features, _lib.RF_VALUES))
+    else:
+        ft = []
+    for x, name in px + [(rsi, "rsi")] + bb + ft:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    nctx = len(_lib.RF_CTX_ROWS)
+    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
+            or ctx.shape[0] != nctx or ctx.shape[1] not in (1, T)):
+        raise ValueError(f"ctx: expected a float64 tensor of shape {(nctx, 1)} or {(nctx, T)} "
+                         f"(rows {_lib.RF_CTX_ROWS})")
+    Tc = int(ctx.shape[1])
+    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
+                               or tuple(ctx_ok.shape) != (Tc,)):
+        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
+    if sym is not None:
+        if len(sym) != len(_RF_SYM):
+            raise ValueError(f"sym: expected {tuple(n for n, _ in _RF_SYM)}")
+        shp = tuple(getattr(sym[0], "shape", ()))
+        if shp not in ((S,), (S, T)):
+            raise ValueError(f"sym: expected tensors of shape {(S,)} or {(S, T)}")
+        for x, (name, dts) in zip(sym, _RF_SYM):
+            if not isinstance(x, torch.Tensor) or x.dtype not in dts or tuple(x.shape) != shp:
+                raise ValueError(f"sym.{name}: expected a {dts[0]} tensor of shape {shp}")
+    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
+        _gate_rows(from_t, "from_t", S)
+    pxs, ld_px = _common_pitch([_check_panel(x, n) for x, n in px])
+    rsi = _check_panel(rsi, "rsi")
+    bbs, ld_bb = _common_pitch([_check_panel(x, n) for x, n in bb])
+    fts, ld_ft = _common_pitch([_check_panel(x, n) for x, n in ft]) if ft else ([], T)
+    others = [ctx] + ([ctx_ok] if ctx_ok is not None else []) + list(sym or ())
+    if not all(x.is_cuda for x in others):
+        raise ValueError("ctx / ctx_ok / sym: expected CUDA tensors (no CPU path)")
+    ld_sym = 0
+    if sym is not None:
+        sym = [x.contiguous() for x in sym]
+        ld_sym = T if sym[0].dim() == 2 else 0
+    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
+        ctx = ctx.contiguous()
+    ld_ctx = int(ctx.stride(0))
+    if ctx_ok is not None and not ctx_ok.is_contiguous():
+        ctx_ok = ctx_ok.contiguous()
+    dev = c.device
+    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    p = _lib.BqRangeFadeParams()
+    for k, val in par.items():
+        setattr(p, k, int(val) if k in _RF_INT_PARAMS else float(val))
+    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
+    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.RF_VALUES])
+    feats = _lib.ptr_array([x.data_ptr() for x in fts]) if fts else None
+    sy = sym if sym is not None else [None] * len(_RF_SYM)
+    st = _lib.load().bq_range_fade_replay(
+        _ptr(pxs[0]), _ptr(pxs[1]), _ptr(pxs[2]), _ptr(pxs[3]), _ptr(pxs[4]), ld_px, _ptr(rsi), _row_stride(rsi),
+        _ptr(bbs[0]), _ptr(bbs[1]), _ptr(bbs[2]), ld_bb, feats, ld_ft, _ptr(ctx), ld_ctx, _ptr(ctx_ok), Tc,
+        _ptr(sy[0]), _ptr(sy[1]), _ptr(sy[2]), _ptr(sy[3]), _ptr(sy[4]), ld_sym, _ptr(lens), _ptr(first_t),
+        _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_range_fade_replay")
+    return status, outs
+
+
 def _join_capacity(ts: torch.Tensor, lens: torch.Tensor | None, bts: torch.Tensor) -> int:
     """Largest per-row count of (candle, benchmark row) matches over the
     candles t >= 1 that join (bench_ts ascending): an upper bound on every

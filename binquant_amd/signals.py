@@ -23,6 +23,11 @@ prefix frame df.iloc[:t + 1]:
                      _resolve_entry, the trend ceiling, the SHORT risk
                      profile, once per candle, the stop-loss cap, one pass
                      (bq_meanrev.hip)
+* range_fade_entry   the decisions of RangeBbRsiMeanReversion.signal()
+                     (strategies/range_bb_rsi_mean_reversion.py:202-274) on the
+                     15m frame: null gate, regime_routing, ADX and z-score
+                     formed in the pass, the two band rejections, local_score,
+                     one pass (bq_rangefade.hip)
 * impulse_rider_features   RelativeStrengthImpulseRider._features
                      (strategies/relative_strength_impulse_rider.py:92-198), one
                      pass (bq_impulse.hip)
@@ -835,6 +840,65 @@ def mean_reversion_fade_entry(o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_
         o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_ok, sym=sym, features=features,
         state=state.tensors() if state is not None else None, first_t=first_t, lens=lens, from_t=from_t,
         columns=columns, **params)
+    return {"status": status, **vals}
+
+
+# bq_range_fade_replay's status codes: where RangeBbRsiMeanReversion.signal() returned, in the method's order
+# (RF_REASONS: regime_routing's reasons by their fixed part; "emit", "no_frame", "not_enough_data" and
+# "adx_too_high" are this library's names for returns the method does not name)
+(RF_EMIT, RF_NO_FRAME, RF_NOT_ENOUGH_DATA, RF_NO_CONTEXT, RF_TRANSITIONING, RF_STRESS, RF_NO_REGIME,
+ RF_REGIME_NOT_RANGE, RF_NO_SYMBOL, RF_SYMBOL_NOT_RANGE, RF_SYMBOL_TRANSITION, RF_SYMBOL_ATR, RF_SYMBOL_BB_WIDTH,
+ RF_ADX_TOO_HIGH, RF_NO_SETUP) = range(15)
+RF_REASONS = dict(enumerate(_lib.RF_REASONS))
+RF_VALUES = _lib.RF_VALUES
+RF_FEATURES = _lib.RF_VALUES[:_lib.RF_NFEATURES]
+RF_CTX_ROWS = _lib.RF_CTX_ROWS
+RF_SYM_KEYS = ("ok", "micro_regime", "micro_transition", "atr_pct", "bb_width")
+RF_LONG, RF_SHORT = 0.0, 1.0   # the `direction` column (bq_direction)
+
+
+def range_fade_entry(o, h, l, c, v, rsi, bb_upper, bb_mid, bb_lower, ctx, ctx_ok=None, *, sym=None, features=None,
+                     first_t=None, lens=None, from_t=None, columns=RF_VALUES, **params):
+    """The decisions of RangeBbRsiMeanReversion.signal()
+    (strategies/range_bb_rsi_mean_reversion.py:202-274) for every candle of a
+    15m panel in one pass (engine.range_fade_replay, bq_range_fade_replay):
+    the frame and null gate, regime_routing, the ADX cut, the two band
+    rejections with their RSI and z-score confirmation, and local_score.
+    Column t of row s = the method on the message whose frame is
+    df_15m.iloc[first_t[s]:t + 1]; candles from_t[s] .. lens[s] - 1 are
+    replayed. o / h / l / c / v / rsi / bb_upper / bb_mid / bb_lower [S, T]
+    float64 (the enriched frame's columns and the three bands as the caller
+    rounds them; current_price is the close). ctx [3, 1] or [3, T] float64
+    (RF_CTX_ROWS; market_regime an index into _lib.MARKET_REGIMES,
+    _lib.MR_NONE for None) and ctx_ok [1] / [T] (False: latest_market_context
+    is None), both on the device. sym: None (no symbol has features in the
+    snapshot) or {RF_SYM_KEYS: tensor}, all [S] or all [S, T]: ok (False:
+    resolve_symbol_features gave None), micro_regime / micro_transition as
+    uint8 indices into _lib.MICRO_REGIMES / _lib.MICRO_TRANSITIONS
+    (_lib.MR_NONE: None), atr_pct, bb_width. features: None to form adx and
+    zscore in the pass over the frame starting at first_t (1e-9 of pandas), or
+    {"adx", "zscore"} (e.g. signals.adx / signals.zscore, which answer on
+    whole rows: first_t = 0 only). params: engine.RANGE_FADE_DEFAULTS' keys.
+
+    Returns {"status": uint8 [S, T] (RF_REASONS; 0 = the message goes out),
+    and the `columns` of RF_VALUES, float64 [S, T], NaN where the method did
+    not reach them: adx from adx_too_high on, zscore from
+    no_bb_rsi_rejection_setup on, direction (RF_LONG / RF_SHORT) and score
+    (local_score, unrounded) where it emits}. The rounding of the bands, the
+    message text and the dispatch stay host steps."""
+    if sym is not None:
+        missing = [k for k in RF_SYM_KEYS if k not in sym]
+        if missing:
+            raise ValueError(f"sym: missing {missing} (expected {RF_SYM_KEYS})")
+        sym = tuple(sym[k] for k in RF_SYM_KEYS)
+    if features is not None:
+        missing = [k for k in RF_FEATURES if k not in features]
+        if missing:
+            raise ValueError(f"features: missing {missing} (expected {RF_FEATURES})")
+        features = tuple(features[k] for k in RF_FEATURES)
+    status, vals = engine.range_fade_replay(
+        o, h, l, c, v, rsi, bb_upper, bb_mid, bb_lower, ctx, ctx_ok, sym=sym, features=features, first_t=first_t,
+        lens=lens, from_t=from_t, columns=columns, **params)
     return {"status": status, **vals}
 
 

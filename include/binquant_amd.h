@@ -60,6 +60,10 @@
  *                         rolling means, _resolve_entry, the trend ceiling, the SHORT
  *                         risk profile, the once-per-candle test and the stop-loss cap
  *                         (strategies/mean_reversion_fade.py:88-212, :224-300)
+ *   bq_range_fade_replay <- RangeBbRsiMeanReversion.signal(): the frame and null
+ *                         gate, regime_routing, _compute_adx, _compute_zscore,
+ *                         _resolve_entry's two band rejections and local_score
+ *                         (strategies/range_bb_rsi_mean_reversion.py:66-274)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -693,6 +697,141 @@ int bq_mean_reversion_replay(const double* open, const double* high, const doubl
                              int64_t ld_sym, const int64_t* lens, const int64_t* first_t, const int64_t* from_t,
                              int64_t S, int64_t T, const bq_mean_reversion_params* params, uint8_t* st_has,
                              int64_t* st_last, uint8_t* status, double* const* values, int64_t ld_out, void* stream);
+
+/*
+ * RangeBbRsiMeanReversion.signal() replayed over a panel of 15m frames
+ * (strategies/range_bb_rsi_mean_reversion.py:202-274, with regime_routing
+ * :66-98, _compute_adx :101-130, _compute_zscore :132-138, the two rejection
+ * tests :140-166 and _resolve_entry :168-196): column t of row s is what
+ * signal() does on the message whose frame is df_15m.iloc[first:t + 1], first =
+ * first_t[s] (NULL: 0). Candles t = max(from_t[s], first) (from_t NULL: 0) ..
+ * lens[s] - 1 (NULL: T) are replayed. The strategy keeps no cooldown entry:
+ * there is no state.
+ * open / high / low / close / volume [S][ld_px] (volume only feeds the null
+ * gate), rsi [S][ld_rsi] (the enriched frame's column), bb_upper / bb_mid /
+ * bb_lower [S][ld_bb] (the bb_high / bb_mid / bb_low the caller passes, as the
+ * caller rounds them); current_price is the candle's close.
+ * features: NULL, or BQ_RF_NFEATURES host pointers to [S][ld_ft] doubles (adx,
+ * zscore; both set): the method's own values, and the pass is point-wise. NULL:
+ * they are formed in the pass over the frame starting at first:
+ *   adx     tr = max(high - low, |high - previous close|, |low - previous
+ *           close|) skipping NaN (the frame's first row: high - low), +DM / -DM
+ *           0.0 on the first row, the three rolling(adx_window, min_periods =
+ *           adx_window) sums, DI = 100 sum / atr_sum, dx = 100 |DI+ - DI-| /
+ *           (DI+ + DI-) and 0.0 wherever that is NaN or the total is 0 (the
+ *           warm-up included: fillna(0.0)), adx = the rolling(adx_window) mean of
+ *           dx, which includes those zeros; 100.0 only while the frame is
+ *           shorter than the window. A NaN true range is excluded and counted:
+ *           dx is 0.0 while a window holds it.
+ *   zscore  (close - mean) / std(ddof=0) over rolling(zscore_window), 0.0 while
+ *           the window reaches before first, holds a NaN close, or is one
+ *           repeated value (std exactly 0).
+ * The sums are direct sums over the window's candles (non-negative terms for
+ * the ADX; closes shifted by the candle's own close for the z-score), within
+ * 1e-9 relative of pandas' online sums. +-inf in a price is outside this
+ * entry's contract.
+ * ctx [3][ld_ctx]: the rows regime_is_transitioning (0 / 1),
+ * market_stress_score, market_regime (the index of the literal in TREND_UP,
+ * TREND_DOWN, RANGE, HIGH_STRESS, TRANSITIONAL; BQ_RF_NONE for None) of
+ * latest_market_context at the candle's message; ctx_T == 1: one context for
+ * every candle, ctx_T == T: one per candle. ctx_ok [ctx_T] bytes, 0 where the
+ * context is None (NULL: present). The symbol's entry in the snapshot
+ * (resolve_symbol_features): sym_ok bytes (0: None; NULL: no symbol has one, the
+ * other four are not read), sym_regime / sym_transition bytes (indices of the
+ * micro_regime / micro_regime_transition literals, BQ_RF_NONE for None),
+ * sym_atr_pct / sym_bb_width doubles; each [S] (ld_sym == 0) or [S][ld_sym].
+ * All device memory.
+ *
+ * Per candle, in the method's order (a NaN fails a comparison as in Python):
+ *   #  condition                                               status
+ *   1  t outside [max(from_t, first), lens)                    NO_FRAME
+ *   2  t + 1 - first < min_candles, or a NaN in open / high /  NOT_ENOUGH_DATA     :212
+ *      low / close / rsi / volume within the frame's last
+ *      min(5, rows) candles
+ *   3  ctx_ok == 0                                             NO_CONTEXT          :71
+ *   4  regime_is_transitioning != 0                            TRANSITIONING       :73
+ *   5  market_stress_score >= max_market_stress                STRESS              :75
+ *   6  market_regime == BQ_RF_NONE                             NO_REGIME           :77
+ *   7  market_regime != RANGE                                  REGIME_NOT_RANGE    :79
+ *   8  sym_ok == 0 (or no snapshot)                            NO_SYMBOL           :81
+ *   9  sym_regime != RANGE (None included)                     SYMBOL_NOT_RANGE    :83
+ *   10 sym_transition in BREAKOUT_UP, BREAKDOWN,               SYMBOL_TRANSITION   :85
+ *      VOLATILITY_EXPANSION
+ *   11 sym_atr_pct > max_symbol_atr_pct                        SYMBOL_ATR          :94
+ *   12 sym_bb_width > max_symbol_bb_width                      SYMBOL_BB_WIDTH     :96
+ *   13 adx > adx_max                                           ADX_TOO_HIGH        :230
+ *   14 neither LONG (close <= bb_mid and rsi <= long_rsi_max   NO_SETUP            :168-196
+ *      and zscore <= long_zscore_max and the bullish
+ *      rejection) nor SHORT (close >= bb_mid and rsi >=
+ *      short_rsi_min and zscore >= short_zscore_min and the
+ *      bearish rejection); LONG is tested first
+ *   0  otherwise                                               EMIT
+ * bullish rejection: range = high - low > 0 (NaN passes this test, as in
+ * Python), low <= bb_lower (1 + band_touch_tolerance), close > open, (min(open,
+ * close) - low) / range >= min_rejection_wick_frac, (close - low) / range >=
+ * long_close_position_min. bearish: high >= bb_upper (1 - band_touch_tolerance),
+ * close < open, (high - max(open, close)) / range >= min_rejection_wick_frac,
+ * (close - low) / range <= short_close_position_max. min / max are Python's.
+ * score = 1.0 + min(|zscore| / 3.0, 1.0) 0.35 + max(0.0, (adx_max - adx) /
+ * adx_max) 0.25 + r 0.25, r = max(0.0, (long_rsi_max - rsi) / long_rsi_max) for
+ * LONG and max(0.0, (rsi - short_rsi_min) / 35.0) for SHORT (the literal 35.0
+ * of :271), unrounded and in that operation order. The rounding of the bands,
+ * the message text and the dispatch stay with the caller.
+ *
+ * status [S][ld_out] bytes (BQ_RF_*), values: NULL or BQ_RF_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_RF_V_* order,
+ * NaN where the method did not reach them: adx on ADX_TOO_HIGH, NO_SETUP and
+ * EMIT, zscore on NO_SETUP and EMIT, direction (bq_direction: 0.0 LONG, 1.0
+ * SHORT) and score on EMIT. params NULL: bq_range_fade_default_params.
+ * BQ_EINVAL, before any launch, unless every ld >= T (ld_sym: or 0), ctx_T is 1
+ * or T, ld_ctx >= ctx_T, the features are both set or the table is NULL, the
+ * thresholds are finite, adx_max != 0, long_rsi_max != 0, min_candles >= 1, 1 <=
+ * adx_window <= BQ_RF_MAX_ADX_WINDOW and 1 <= zscore_window <=
+ * BQ_RF_MAX_ZSCORE_WINDOW (a window and what it carries from the previous
+ * 64-candle step fit one step). S == 0 or T == 0: BQ_OK.
+ */
+#define BQ_RF_MAX_ADX_WINDOW 32
+#define BQ_RF_MAX_ZSCORE_WINDOW 64
+#define BQ_RF_NVALUES 4
+#define BQ_RF_NFEATURES 2
+#define BQ_RF_NONE 255
+#define BQ_RF_REGIME_RANGE 2                    /* market_regime / micro_regime "RANGE" */
+#define BQ_RF_TRANSITION_VOLATILITY_EXPANSION 0 /* micro_regime_transition literals */
+#define BQ_RF_TRANSITION_BREAKOUT_UP 1
+#define BQ_RF_TRANSITION_BREAKDOWN 2
+typedef struct bq_range_fade_params {
+  int32_t min_candles;               /* 40  MIN_CANDLES */
+  int32_t adx_window;                /* 14  ADX_WINDOW */
+  int32_t zscore_window;             /* 20  ZSCORE_WINDOW */
+  int32_t reserved;                  /* 0 */
+  double adx_max;                    /* 32  ADX_MAX */
+  double long_rsi_max;               /* 35  LONG_RSI_MAX */
+  double short_rsi_min;              /* 65  SHORT_RSI_MIN */
+  double long_zscore_max;            /* -2  LONG_ZSCORE_MAX */
+  double short_zscore_min;           /* 2   SHORT_ZSCORE_MIN */
+  double band_touch_tolerance;       /* 0.002 BAND_TOUCH_TOLERANCE */
+  double max_market_stress;          /* 0.35 MAX_MARKET_STRESS */
+  double max_symbol_atr_pct;         /* 0.04 MAX_SYMBOL_ATR_PCT */
+  double max_symbol_bb_width;        /* 0.08 MAX_SYMBOL_BB_WIDTH */
+  double min_rejection_wick_frac;    /* 0.30 MIN_REJECTION_WICK_FRAC */
+  double long_close_position_min;    /* 0.55 LONG_CLOSE_POSITION_MIN */
+  double short_close_position_max;   /* 0.45 SHORT_CLOSE_POSITION_MAX */
+} bq_range_fade_params;
+enum { BQ_RF_EMIT = 0, BQ_RF_NO_FRAME, BQ_RF_NOT_ENOUGH_DATA, BQ_RF_NO_CONTEXT, BQ_RF_TRANSITIONING, BQ_RF_STRESS,
+       BQ_RF_NO_REGIME, BQ_RF_REGIME_NOT_RANGE, BQ_RF_NO_SYMBOL, BQ_RF_SYMBOL_NOT_RANGE, BQ_RF_SYMBOL_TRANSITION,
+       BQ_RF_SYMBOL_ATR, BQ_RF_SYMBOL_BB_WIDTH, BQ_RF_ADX_TOO_HIGH, BQ_RF_NO_SETUP };
+enum { BQ_RF_V_ADX = 0, BQ_RF_V_ZSCORE, BQ_RF_V_DIRECTION, BQ_RF_V_SCORE };
+enum { BQ_RF_CTX_TRANSITIONING = 0, BQ_RF_CTX_STRESS, BQ_RF_CTX_REGIME };
+void bq_range_fade_default_params(bq_range_fade_params* p);
+int bq_range_fade_replay(const double* open, const double* high, const double* low, const double* close,
+                         const double* volume, int64_t ld_px, const double* rsi, int64_t ld_rsi,
+                         const double* bb_upper, const double* bb_mid, const double* bb_lower, int64_t ld_bb,
+                         const double* const* features, int64_t ld_ft, const double* ctx, int64_t ld_ctx,
+                         const uint8_t* ctx_ok, int64_t ctx_T, const uint8_t* sym_ok, const uint8_t* sym_regime,
+                         const uint8_t* sym_transition, const double* sym_atr_pct, const double* sym_bb_width,
+                         int64_t ld_sym, const int64_t* lens, const int64_t* first_t, const int64_t* from_t,
+                         int64_t S, int64_t T, const bq_range_fade_params* params, uint8_t* status,
+                         double* const* values, int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t

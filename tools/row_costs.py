@@ -96,6 +96,15 @@ rows = {
     "mean_reversion_fade_entry": lambda: signals.mean_reversion_fade_entry(
         o, h, l, c, v, atr, c, ts, torch.tensor([[0.1], [0.2], [0.3], [0.0], [0.0]], dtype=torch.float64,
                                                  device="cuda")),
+    # RangeBbRsiMeanReversion.signal()'s decisions, every output column, adx and zscore formed in the pass (rsi: the
+    # close as a stand-in column, the bands the close, one RANGE context for every candle, a calm snapshot [S])
+    "range_fade_entry": lambda: signals.range_fade_entry(
+        o, h, l, c, v, c, c, c, c, torch.tensor([[0.0], [0.1], [2.0]], dtype=torch.float64, device="cuda"),
+        sym={"ok": torch.ones(S, dtype=torch.uint8, device="cuda"),
+             "micro_regime": torch.full((S,), 2, dtype=torch.uint8, device="cuda"),
+             "micro_transition": torch.full((S,), 255, dtype=torch.uint8, device="cuda"),
+             "atr_pct": torch.full((S,), 0.01, dtype=torch.float64, device="cuda"),
+             "bb_width": torch.full((S,), 0.02, dtype=torch.float64, device="cuda")}),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
