@@ -137,6 +137,22 @@ __device__ __forceinline__ int64_t readlane_i64(int64_t x, int lane) {
   return ((int64_t)hi << 32) | (int64_t)lo;
 }
 
+// Python's max(a, b) / min(a, b): the first argument unless the second wins the compare
+__device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
+__device__ __forceinline__ double py_min(double a, double b) { return b < a ? b : a; }
+// math.isfinite
+__device__ __forceinline__ bool is_finite(double x) { return x - x == 0.0; }
+
+// bits [a, b] of a 64-bit ballot, 0 <= a <= b <= 63
+__device__ __forceinline__ uint64_t ballot_bits(int a, int b) { return (~0ull >> (63 - b)) & (~0ull << a); }
+// the window [lane - w + 1, lane] of this step's ballot B and the previous step's BP holds a set bit (1 <= w <= 64)
+__device__ __forceinline__ bool window_hit(uint64_t B, uint64_t BP, int w, int lane) {
+  const int w0 = lane - w + 1;
+  bool hit = (B & ballot_bits(w0 > 0 ? w0 : 0, lane)) != 0;
+  if (w0 < 0) hit = hit || (BP >> (WAVE + w0)) != 0;
+  return hit;
+}
+
 // a per-row int64 (lens / first_t / from_t of the replay kernels; NULL: dflt), clamped to [0, T]
 __device__ __forceinline__ int clamp_row(const int64_t* v, int64_t s, int64_t dflt, int T) {
   const int64_t x = v ? v[s] : dflt;

@@ -56,7 +56,6 @@ struct ImpulseArgs {
 };
 
 __device__ __forceinline__ bool pos_finite(double x) { return x > 0.0 && x < __builtin_inf(); }
-__device__ __forceinline__ bool is_finite(double x) { return x - x == 0.0; }
 
 __global__ __launch_bounds__(IR_NT) void impulse_kernel(const ImpulseArgs A) {
   __shared__ double sC[IR_HC + IR_TILE];

@@ -6,9 +6,7 @@
 // frame is df.iloc[first_t[s]:t + 1], after the messages of all earlier
 // candles of the row (the rule table: include/binquant_amd.h).
 //
-// price_tracker_kernel: spike_fade_kernel's mapping (bq_spikefade.hip) — one
-// wave per row, 64 candles per step, every column one coalesced load per step,
-// the next step's columns loaded before this step's walk.
+// price_tracker_kernel: the wave-per-row replay mapping (bq_replay.h).
 //   1. the gates and both scores are point-wise, in the method's operation
 //      order. tail(tail_rows).isnull() looks back across the step edge: the
 //      previous step's NaN ballot is carried (the first replayed step forms it
@@ -19,34 +17,29 @@
 //      whose close_time lies outside [last, last + cooldown_ms) emits, the P
 //      lanes before it are COOLDOWN, last moves to that lane's close_time.
 //   3. trend_score, when not given: closes.ewm(span, adjust=False).mean() for
-//      both spans as affine maps y -> la y + lb x, one DPP wave scan per step
-//      and series with the carry of the previous step; steps between first_t's
-//      and from_t's load close only. A row that meets a missing or infinite
-//      close inside its frame continues from that step with pandas' own
-//      recursion, serially over the step's lanes (wave-uniform state).
+//      both spans through bq_replay.h's ewm_step (two series seeded at first_t,
+//      one input); steps between first_t's and from_t's load close only.
 //   Up to 9 x 8 B in (the context rows: L2-resident) and 2 + 6 x 8 B out per
 //   candle; no LDS, no atomics, no scratch.
 //   Resource usage (gfx950 cross-compile, -O3; <EMA, HLV>): in-pass EMA with
 //   high / low / volume 114 VGPRs, 106 SGPRs, 4 waves / SIMD; in-pass EMA
-//   without them 100 / 106 / 4; trend_score given 90 / 105 / 5 and 76 / 106 /
-//   6. No spills, scratch 0, LDS 0 in all four.
+//   without them 100 / 105 / 4; trend_score given 88 / 106 / 5 and 72 / 106 /
+//   7. No spills, scratch 0, LDS 0 in all four.
 //
 // Domain: close_time strictly ascending within [first_t, lens).
-#include "bq_device.h"
+#include "bq_replay.h"
 #include "binquant_amd.h"
 
 #include <string.h>
 
 namespace bq {
 
-constexpr int PT_NT = 256;            // threads: PT_NT / WAVE rows per workgroup
-constexpr int PT_WPB = PT_NT / WAVE;
-
-// one ewm series: pandas' alpha / old-weight factor / divisor, the affine map
-// y -> la y + lb x, apow[j] = la^(2^j)
-struct PtEwm {
-  double alpha, om, la, lb;
-  double apow[7];
+// the scanned series: ewm(span_fast) and ewm(span_slow) of close, seeded at first_t
+struct PtSeries {
+  static constexpr int NE = 2, NK = 2, SWITCH = 0;
+  static constexpr int set(int e) { return e; }
+  static constexpr int seed(int) { return 0; }
+  static constexpr bool min_periods(int) { return false; }
 };
 
 struct PtArgs {
@@ -57,7 +50,7 @@ struct PtArgs {
   int64_t ld_px, ld_ind, ld_ct, ld_tr, ld_rs, ld_out, S;
   int T, ctx_T, ld_ctx, omask;
   bq_price_tracker_params p;
-  PtEwm ew[2];   // span_fast, span_slow
+  Ewm ew[2];   // span_fast, span_slow
   uint8_t* st_has;
   int64_t* st_last;
   uint8_t *status, *detail;
@@ -69,36 +62,21 @@ struct PtStep {
   int64_t ct;
 };
 
-// shared/utils.py:12-17 and Python's min(a, b), as bq_regime.hip states them
+// shared/utils.py:12-17, as bq_regime.hip states them
 __device__ __forceinline__ double pt_clamp(double x, double lo = -1.0, double hi = 1.0) {
   const double m = x < hi ? x : hi;   // min(high, value)
   return m > lo ? m : lo;              // max(low, m)
 }
 __device__ __forceinline__ double pt_nneg(double x) { return x > 0.0 ? x : 0.0; }   // max(0.0, value)
-__device__ __forceinline__ double pt_min(double a, double b) { return b < a ? b : a; }
-
-// bits [a, b] of a 64-bit ballot, 0 <= a <= b <= 63
-__device__ __forceinline__ uint64_t pt_bits(int a, int b) { return (~0ull >> (63 - b)) & (~0ull << a); }
-
-// The thresholds, weights and ewm constants (~75 dwords) are read from the
-// kernarg segment where a step uses them, through a pointer the compiler
-// cannot see through: as loop invariants they would all be held in SGPRs
-// beside the 20 row pointers, and spill. They stay in the scalar cache.
-typedef const __attribute__((address_space(4))) PtArgs* PtKarg;
-__device__ __forceinline__ PtKarg pt_karg() {
-  PtKarg k = (PtKarg)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return k;
-}
 
 template <bool EMA, bool HLV>
-__global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
+__global__ __launch_bounds__(RP_NT) void price_tracker_kernel(const PtArgs A) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t s = (int64_t)blockIdx.x * PT_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int64_t s = replay_row_index();
   if (s >= A.S) return;   // whole wave
   const int T = A.T;
-  const int len = clamp_row(A.lens, s, T, T), first = clamp_row(A.first, s, 0, T), from0 = clamp_row(A.from, s, 0, T);
-  const int from = from0 > first ? from0 : first;   // a candle before first_t has an empty frame: no message
+  const ReplayRow R = replay_row(A.lens, A.first, A.from, s, T);
+  const int len = R.len, first = R.first, from = R.from;
   const int TR0 = A.p.tail_rows;
   constexpr bool ema = EMA;   // trend_score NULL: formed in the pass
   const double* __restrict__ cl = A.close + s * A.ld_px;
@@ -115,21 +93,12 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
   const double* __restrict__ rsr = A.rs + s * (A.ld_rs ? A.ld_rs : 1);
   const int64_t* __restrict__ ctp = A.ct + s * A.ld_ct;
   const double rs_row = A.ld_rs ? 0.0 : rsr[0];
-  // the outputs as per-lane pointers held in VGPRs (candle `lane` of the row;
-  // a step adds t0), their presence as the bits of A.omask: eight more row
-  // pointers and null flags would not fit the SGPR file beside the inputs'
-  const int64_t orow = s * A.ld_out + lane;
-  uint8_t* st_out = A.status + orow;
-  uint8_t* dt_out = A.detail + orow;
-  asm volatile("" : "+v"(st_out), "+v"(dt_out));
-  double* vout[BQ_PT_NVALUES];
+  // omask bit k: a BQ_PT_V_*; bit BQ_PT_NVALUES: detail, a per-lane pointer like the others
+  ReplayOut<PtArgs, BQ_PT_NVALUES> O(A.status, A.ld_out, s, lane);
 #pragma unroll
-  for (int k = 0; k < BQ_PT_NVALUES; ++k) {
-    vout[k] = A.val[k] + orow;
-    asm volatile("" : "+v"(vout[k]));
-  }
-  // k: a BQ_PT_V_*; BQ_PT_NVALUES: detail (tested where a step stores, not held as eight lane masks)
-  auto has_out = [&](int k) { return (pt_karg()->omask >> k) & 1; };
+  for (int k = 0; k < BQ_PT_NVALUES; ++k) O.set(k, A.val[k]);
+  uint8_t* dt_out = A.detail + O.orow;
+  asm volatile("" : "+v"(dt_out));
 
   // the row's cooldown entry: wave-uniform from here on
   bool has = A.st_has && A.st_has[s] != 0;
@@ -157,9 +126,8 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
     return x;
   };
 
-  const int b0 = from & ~(WAVE - 1);       // the first step that holds a replayed candle
-  const int e0 = first & ~(WAVE - 1);      // the first step that holds a candle of the frame
-  const bool any = from < len;
+  const int b0 = R.b0(), e0 = R.e0();
+  const bool any = R.any();
 
   // the NaN ballot of the step before b0: only its last TR - 1 candles matter
   uint64_t PB = 0;
@@ -174,73 +142,13 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
     PB = __builtin_bitreverse64(__ballot(bad));   // candle b0 - 1 - j: bit 63 - j
   }
 
-  // ---- the in-pass ewm series
-  double lpow[2] = {0.0, 0.0}, rpow[2] = {0.0, 0.0}, carry[2] = {0.0, 0.0};
-  bool serial = false;
-  double swv[2] = {qnan(), qnan()}, sowt[2] = {1.0, 1.0};
-  if (ema) {
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      lpow[e] = pow_bits<7>(A.ew[e].apow, lane + 1);
-      rpow[e] = pow_bits<5>(A.ew[e].apow, (lane & 15) + 1);
-    }
-  }
-  // candles t0 .. t0 + 63 of both series into y (every lane executes it)
+  // ---- the in-pass ewm series: candles t0 .. t0 + 63 of both into y (every lane executes it)
+  EwmState<PtSeries::NE, PtSeries::NK> ES;
+  ewm_init<PtSeries>(ES, A.ew, lane, ema);
   auto ema_step = [&](double c, int t0, double (&y)[2]) {
-    const int t = t0 + lane;
     const double x = win_val(c);   // ewm: +-inf is missing
-    if (!serial && __ballot(t >= first && t < len && !(x == x))) {   // wave-uniform: the row turns serial here
-      serial = true;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        swv[e] = t0 > first ? carry[e] : qnan();   // candles first .. t0 - 1 were all observations
-        sowt[e] = 1.0;
-      }
-    }
-    const PtKarg K = pt_karg();
-    if (serial) {   // pandas' recursion over the step, both series
-      const double om[2] = {K->ew[0].om, K->ew[1].om}, alpha[2] = {K->ew[0].alpha, K->ew[1].alpha};
-      const int i0 = first > t0 ? first - t0 : 0, n = len - t0 < WAVE ? len - t0 : WAVE;
-      y[0] = y[1] = qnan();
-      for (int i = i0; i < n; ++i) {
-        const double cur = readlane_f64(x, i);
-        const bool obs = cur == cur;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          double wv = swv[e], owt = sowt[e];
-          if (t0 + i == first) {
-            wv = cur;
-            owt = 1.0;
-          } else if (wv == wv) {
-            owt *= om[e];
-            if (obs) {
-              if (wv != cur) {
-                wv = owt * wv + alpha[e] * cur;
-                wv /= owt + alpha[e];
-              }
-              owt = 1.0;
-            }
-          } else if (obs) {
-            wv = cur;
-          }
-          swv[e] = wv;
-          sowt[e] = owt;
-          asm volatile("" : "+v"(swv[e]), "+v"(sowt[e]));
-          if (lane == i) y[e] = wv;
-        }
-      }
-      return;
-    }
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const double ap[5] = {K->ew[e].apow[0], K->ew[e].apow[1], K->ew[e].apow[2], K->ew[e].apow[3], K->ew[e].apow[4]};
-      // zero before first_t, the seed at first_t: its lane receives a zero carry
-      const double b = t < first ? 0.0 : (t == first ? x : K->ew[e].lb * x);
-      const double inc = wave_scan_affine_dpp_rp(b, ap, rpow[e], lane);
-      y[e] = fma(lpow[e], carry[e], inc);
-      carry[e] = readlane_f64(y[e], WAVE - 1);
-      asm volatile("" : "+v"(carry[e]));   // the series' uniform state lives in VGPRs, not beside the row pointers
-    }
+    const double xs[2] = {x, x};
+    ewm_step<PtSeries>(ES, kernarg<PtArgs>()->ew, xs, t0, lane, first, len, 0, y);
   };
 
   PtStep nxt = {};
@@ -248,11 +156,8 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
     const int t = t0 + lane;
     if (!any || t0 + WAVE <= from || t0 >= len) {   // no replayed candle in this step
       if (t < T) {
-        st_out[t0] = BQ_PT_NO_FRAME;
-        if (has_out(BQ_PT_NVALUES)) dt_out[t0] = 0;
-#pragma unroll
-        for (int k = 0; k < BQ_PT_NVALUES; ++k)
-          if (has_out(k)) vout[k][t0] = qnan();
+        O.no_frame(t0, BQ_PT_NO_FRAME);
+        if (O.has(BQ_PT_NVALUES)) dt_out[t0] = 0;
       }
       if (ema && any && t0 >= e0 && t0 < b0) {   // the series run from first_t on: close alone
         double y[2];
@@ -264,16 +169,14 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
     const PtStep cur = nxt;
     if (t0 + WAVE < len) nxt = load_step(t0 + WAVE);   // in flight during this step's walk
     const bool valid = t >= from && t < len;
-    const PtKarg K = pt_karg();
+    const Karg<PtArgs> K = kernarg<PtArgs>();
     const auto& P = K->p;
     const int TR = P.tail_rows;
     const int64_t cd = P.cooldown_ms;
 
     // :174-181 the frame and null gate
     const uint64_t NB = __ballot(t >= first && t < len && null_of(cur));
-    const int w0 = lane - TR + 1;
-    bool tailbad = (NB & pt_bits(w0 > 0 ? w0 : 0, lane)) != 0;
-    if (w0 < 0) tailbad = tailbad || (PB >> (WAVE + w0)) != 0;
+    const bool tailbad = window_hit(NB, PB, TR, lane);
     PB = NB;
     const bool ready = t + 1 - first >= P.min_history && !tailbad;
     // :194 (compares in the method's direction: a NaN fails)
@@ -281,7 +184,7 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
     // :198-203
     const double local = ((1.0 + pt_nneg((P.rsi_max - cur.rsi) / P.rsi_max) * P.w_rsi) +
                           pt_nneg((P.mfi_max - cur.mfi) / P.mfi_max) * P.w_mfi) +
-                         pt_min(fabs(cur.macd) * P.macd_scale, 1.0) * P.w_macd;
+                         py_min(fabs(cur.macd) * P.macd_scale, 1.0) * P.w_macd;
     // :204-210
     double trend = cur.tr;
     if (ema) {
@@ -290,13 +193,9 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
       trend = y[1] != 0.0 ? (y[0] - y[1]) / fabs(y[1]) : 0.0;
     }
     // the context of the candle's message
-    unsigned ci = K->ctx_T == 1 ? 0u : (unsigned)(t < T ? t : 0);
-    asm volatile("" : "+v"(ci));   // vector loads also where the context is one column
-    const unsigned ldc = (unsigned)K->ld_ctx;
-    const uint8_t* cokp = K->ctx_ok;
-    const double* ctxp = K->ctx;
-    const bool cok = cokp ? cokp[ci] != 0 : true;
-    const double conf = ctxp[ci], tail_l = ctxp[ldc + ci], btc = ctxp[2 * ldc + ci], stress = ctxp[3 * ldc + ci];
+    double cx[4];
+    const bool cok = ctx_load(K, ctx_index(K, t, T), cx);
+    const double conf = cx[0], tail_l = cx[1], btc = cx[2], stress = cx[3];
     // RuleBasedMarketContextModel.evaluate, LONG (context_scoring.py:22-85)
     double conf_s = 0.0, fol = 0.0, adv = 0.0, sup = 0.0;
     if (cok && !(conf <= 0.0)) {
@@ -353,15 +252,15 @@ __global__ __launch_bounds__(PT_NT) void price_tracker_kernel(const PtArgs A) {
     }
 
     if (t < T) {
-      st_out[t0] = (uint8_t)st;
-      if (has_out(BQ_PT_NVALUES)) dt_out[t0] = (uint8_t)dt;
+      O.st[t0] = (uint8_t)st;
+      if (O.has(BQ_PT_NVALUES)) dt_out[t0] = (uint8_t)dt;
       const bool reached = st == BQ_PT_EMIT || st >= BQ_PT_NO_CONTEXT;
-      if (has_out(BQ_PT_V_LOCAL)) vout[BQ_PT_V_LOCAL][t0] = reached ? local : qnan();
-      if (has_out(BQ_PT_V_TREND)) vout[BQ_PT_V_TREND][t0] = reached ? trend : qnan();
-      if (has_out(BQ_PT_V_FOLLOWTHROUGH)) vout[BQ_PT_V_FOLLOWTHROUGH][t0] = reached ? fol : qnan();
-      if (has_out(BQ_PT_V_RISK)) vout[BQ_PT_V_RISK][t0] = reached ? adv : qnan();
-      if (has_out(BQ_PT_V_SUPPORT)) vout[BQ_PT_V_SUPPORT][t0] = reached ? sup : qnan();
-      if (has_out(BQ_PT_V_ADJUSTED)) vout[BQ_PT_V_ADJUSTED][t0] = reached ? adj : qnan();
+      if (O.has(BQ_PT_V_LOCAL)) O.val[BQ_PT_V_LOCAL][t0] = reached ? local : qnan();
+      if (O.has(BQ_PT_V_TREND)) O.val[BQ_PT_V_TREND][t0] = reached ? trend : qnan();
+      if (O.has(BQ_PT_V_FOLLOWTHROUGH)) O.val[BQ_PT_V_FOLLOWTHROUGH][t0] = reached ? fol : qnan();
+      if (O.has(BQ_PT_V_RISK)) O.val[BQ_PT_V_RISK][t0] = reached ? adv : qnan();
+      if (O.has(BQ_PT_V_SUPPORT)) O.val[BQ_PT_V_SUPPORT][t0] = reached ? sup : qnan();
+      if (O.has(BQ_PT_V_ADJUSTED)) O.val[BQ_PT_V_ADJUSTED][t0] = reached ? adj : qnan();
     }
   }
   if (A.st_has && lane == 0) {
@@ -395,19 +294,6 @@ extern "C" void bq_price_tracker_default_params(bq_price_tracker_params* p) {
   p->cooldown_ms = 12 * (int64_t)300000;   // ENTRY_COOLDOWN_BARS x DEFAULT_INTERVAL_MS
 }
 
-namespace {
-// pandas: alpha = 1 / (1 + com), com = (span - 1) / 2
-void pt_ewm_consts(bq::PtEwm& E, double span) {
-  E.alpha = 1.0 / (1.0 + (span - 1.0) / 2.0);
-  E.om = 1.0 - E.alpha;
-  const double den = E.om + E.alpha;
-  E.la = E.om / den;
-  E.lb = E.alpha / den;
-  E.apow[0] = E.la;
-  for (int j = 1; j < 7; ++j) E.apow[j] = E.apow[j - 1] * E.apow[j - 1];
-}
-}  // namespace
-
 extern "C" int bq_price_tracker_replay(const double* close, const double* high, const double* low,
                                        const double* volume, int64_t ld_px, const double* rsi, const double* macd,
                                        const double* mfi, int64_t ld_ind, const int64_t* close_time, int64_t ld_ct,
@@ -429,17 +315,15 @@ extern "C" int bq_price_tracker_replay(const double* close, const double* high, 
   if (params) A.p = *params;
   else bq_price_tracker_default_params(&A.p);
   const bq_price_tracker_params& p = A.p;
-  const double fin[] = {p.rsi_max,        p.macd_max,    p.mfi_max,        p.w_rsi,           p.w_mfi,
-                        p.w_macd,         p.macd_scale,  p.context_weight, p.risk_weight,     p.support_weight,
-                        p.min_followthrough, p.max_risk, p.min_confidence};
-  for (double v : fin)
-    if (!(v - v == 0.0)) return BQ_EINVAL;
+  if (!all_finite({p.rsi_max, p.macd_max, p.mfi_max, p.w_rsi, p.w_mfi, p.w_macd, p.macd_scale, p.context_weight,
+                   p.risk_weight, p.support_weight, p.min_followthrough, p.max_risk, p.min_confidence}))
+    return BQ_EINVAL;
   if (p.min_history < 1 || p.tail_rows < 1 || p.tail_rows > BQ_PT_MAX_TAIL_ROWS || p.span_fast < 1 ||
       p.span_slow < 1 || p.cooldown_ms < 0 || p.rsi_max == 0.0 || p.mfi_max == 0.0)
     return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t blocks = (S + PT_WPB - 1) / PT_WPB;
-  if (blocks > 0x7fffffff) return BQ_EINVAL;
+  int64_t blocks;
+  if (!replay_blocks(S, blocks)) return BQ_EINVAL;
   A.close = close;
   const bool hlv = high || low || volume;   // a NULL one of the three: close stands in (tested anyway)
   A.high = high ? high : close;
@@ -466,18 +350,15 @@ extern "C" int bq_price_tracker_replay(const double* close, const double* high, 
   A.S = S;
   A.T = (int)T;
   A.ctx_T = (int)ctx_T;
-  pt_ewm_consts(A.ew[0], (double)p.span_fast);   // close.ewm(span=9, adjust=False) (:204)
-  pt_ewm_consts(A.ew[1], (double)p.span_slow);   // close.ewm(span=21, adjust=False) (:205)
+  ewm_consts(A.ew[0], ewm_alpha_span((double)p.span_fast));   // close.ewm(span=9, adjust=False) (:204)
+  ewm_consts(A.ew[1], ewm_alpha_span((double)p.span_slow));   // close.ewm(span=21, adjust=False) (:205)
   A.st_has = st_has;
   A.st_last = st_last;
   A.status = status;
   A.detail = detail;
-  for (int k = 0; k < BQ_PT_NVALUES; ++k) {
-    A.val[k] = values ? values[k] : nullptr;
-    A.omask |= A.val[k] ? 1 << k : 0;
-  }
+  replay_values(A.val, A.omask, values);
   A.omask |= detail ? 1 << BQ_PT_NVALUES : 0;
-  const dim3 grid((unsigned)blocks), block(PT_NT);
+  const dim3 grid((unsigned)blocks), block(RP_NT);
   hipStream_t st = (hipStream_t)stream;
   if (trend_score && hlv) hipLaunchKernelGGL((price_tracker_kernel<false, true>), grid, block, 0, st, A);
   else if (trend_score) hipLaunchKernelGGL((price_tracker_kernel<false, false>), grid, block, 0, st, A);

@@ -6,9 +6,7 @@
 // on the message whose frame is df_15m.iloc[first_t[s]:t + 1] (the rule table:
 // include/binquant_amd.h). The strategy keeps no cooldown entry: no state.
 //
-// range_fade_kernel: mean_reversion_kernel's mapping (bq_meanrev.hip) — one wave
-// per row, 64 candles per step, every column one coalesced 512-byte load per
-// step, the next step's columns loaded before this step's arithmetic.
+// range_fade_kernel: the wave-per-row replay mapping (bq_replay.h).
 //   1. <FEAT = true> forms adx and zscore over the frame starting at first_t.
 //      The windows are finite, so a replayed candle reads no further back than
 //      the step before its own: the features are formed from the step before
@@ -59,15 +57,13 @@
 //
 // Domain: prices finite or NaN inside the frame (+-inf in a price is outside
 // this entry's contract and untested).
-#include "bq_device.h"
+#include "bq_replay.h"
 #include "binquant_amd.h"
 
 #include <string.h>
 
 namespace bq {
 
-constexpr int RF_NT = 256;            // threads: RF_NT / WAVE rows per workgroup
-constexpr int RF_WPB = RF_NT / WAVE;
 constexpr int RF_TAIL = 5;            // df[required_cols].tail(5) (:212)
 
 struct RfArgs {
@@ -89,12 +85,6 @@ struct RfStep {
   double o, h, l, c, v, rsi, bbu, bbm, bbl;
   double f[BQ_RF_NFEATURES];
 };
-
-// Python's max(a, b) / min(a, b): the first argument unless the second wins the compare
-__device__ __forceinline__ double rf_pymax(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ double rf_pymin(double a, double b) { return b < a ? b : a; }
-// bits [a, b] of a 64-bit ballot, 0 <= a <= b <= 63
-__device__ __forceinline__ uint64_t rf_bits(int a, int b) { return (~0ull >> (63 - b)) & (~0ull << a); }
 
 // the k-th move of one lane to the right along the 128 candles (previous step q, this step x): x's lane i receives
 // lane i - 1, lane 0 the previous step's lane 64 - k
@@ -119,31 +109,14 @@ __device__ __forceinline__ void rf_walk(int w, F&& f) {
   if (k < w) f(k);
 }
 
-// the window [lane - w + 1, lane] of this step's ballot B and the previous step's BP holds a set bit (1 <= w <= 64)
-__device__ __forceinline__ bool rf_window_hit(uint64_t B, uint64_t BP, int w, int lane) {
-  const int w0 = lane - w + 1;
-  bool hit = (B & rf_bits(w0 > 0 ? w0 : 0, lane)) != 0;
-  if (w0 < 0) hit = hit || (BP >> (WAVE + w0)) != 0;
-  return hit;
-}
-
-// The thresholds are read from the kernarg segment where a step uses them, through a pointer the compiler cannot
-// see through (bq_meanrev.hip): as loop invariants they would be held in SGPRs beside the row pointers.
-typedef const __attribute__((address_space(4))) RfArgs* RfKarg;
-__device__ __forceinline__ RfKarg rf_karg() {
-  RfKarg k = (RfKarg)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(k));
-  return k;
-}
-
 template <bool FEAT>
-__global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
+__global__ __launch_bounds__(RP_NT) void range_fade_kernel(const RfArgs A) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t s = (int64_t)blockIdx.x * RF_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int64_t s = replay_row_index();
   if (s >= A.S) return;   // whole wave
   const int T = A.T;
-  const int len = clamp_row(A.lens, s, T, T), first = clamp_row(A.first, s, 0, T), from0 = clamp_row(A.from, s, 0, T);
-  const int from = from0 > first ? from0 : first;   // a candle before first_t has an empty frame: no message
+  const ReplayRow R = replay_row(A.lens, A.first, A.from, s, T);
+  const int len = R.len, first = R.first, from = R.from;
   const double* __restrict__ op = A.open + s * A.ld_px;
   const double* __restrict__ hp = A.high + s * A.ld_px;
   const double* __restrict__ lp = A.low + s * A.ld_px;
@@ -153,18 +126,9 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
   const double* __restrict__ bup = A.bbu + s * A.ld_bb;
   const double* __restrict__ bmp = A.bbm + s * A.ld_bb;
   const double* __restrict__ blp = A.bbl + s * A.ld_bb;
-  // the outputs as per-lane pointers held in VGPRs (candle `lane` of the row; a step adds t0), their presence as
-  // the bits of A.omask
-  const int64_t orow = s * A.ld_out + lane;
-  uint8_t* st_out = A.status + orow;
-  asm volatile("" : "+v"(st_out));
-  double* vout[BQ_RF_NVALUES];
+  ReplayOut<RfArgs, BQ_RF_NVALUES> O(A.status, A.ld_out, s, lane);
 #pragma unroll
-  for (int k = 0; k < BQ_RF_NVALUES; ++k) {
-    vout[k] = A.val[k] + orow;
-    asm volatile("" : "+v"(vout[k]));
-  }
-  auto has_out = [&](int k) { return (rf_karg()->omask >> k) & 1; };
+  for (int k = 0; k < BQ_RF_NVALUES; ++k) O.set(k, A.val[k]);
 
   // one step's columns, candle tb + lane (NaN past the panel's end)
   auto load_step = [&](int tb) {
@@ -185,19 +149,18 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
       if (FEAT) {
         x.f[k] = 0.0;
       } else {
-        const double* fp = rf_karg()->feat[k] + s * rf_karg()->ld_ft;
+        const double* fp = kernarg<RfArgs>()->feat[k] + s * kernarg<RfArgs>()->ld_ft;
         x.f[k] = in ? fp[u] : qnan();
       }
     }
     return x;
   };
 
-  const int b0 = from & ~(WAVE - 1);       // the first step that holds a replayed candle
-  const int e0 = first & ~(WAVE - 1);      // the first step that holds a candle of the frame
   // the first step the features are formed on: the windows are finite (2 adx_window - 1 <= 63 candles for the ADX,
   // zscore_window <= 64 closes), so a replayed candle reads no further back than the step before its own
+  const int b0 = R.b0(), e0 = R.e0();
   const int f0 = b0 - WAVE > e0 ? b0 - WAVE : e0;
-  const bool any = from < len;
+  const bool any = R.any();
 
   // ---- the in-pass features' state: lane 63's candle, the previous step's series and missing-value ballots
   double h_carry = qnan(), l_carry = qnan(), c_carry = qnan();
@@ -211,7 +174,7 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
   auto feat_step = [&](double h, double l, double c, int t0, bool need, double (&f)[BQ_RF_NFEATURES]) {
     const int t = t0 + lane;
     const int r = t - first;   // the frame's row
-    const RfKarg K = rf_karg();
+    const Karg<RfArgs> K = kernarg<RfArgs>();
     const int W = K->p.adx_window, WZ = K->p.zscore_window;
     double ph = dpp_f64<DPP_WAVE_SHR1>(h), pl = dpp_f64<DPP_WAVE_SHR1>(l), pc = dpp_f64<DPP_WAVE_SHR1>(c);
     if (lane == 0) {
@@ -248,7 +211,7 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
       });
     }
     const bool ready = r + 1 >= W;   // min_periods = window
-    const double asum = (ready && !rf_window_hit(TB, tb_prev, W, lane)) ? st : qnan();
+    const double asum = (ready && !window_hit(TB, tb_prev, W, lane)) ? st : qnan();
     const double pdi = 100.0 * (ready ? sp : qnan()) / asum, mdi = 100.0 * (ready ? sm : qnan()) / asum;   // :120-121
     const double tot = pdi + mdi;
     double dx = tot != 0.0 ? 100.0 * fabs(pdi - mdi) / tot : qnan();   // :123-127
@@ -281,7 +244,7 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
       });
     }
     double z = 0.0;
-    if (r + 1 >= WZ && !rf_window_hit(CB, cb_prev, WZ, lane)) {
+    if (r + 1 >= WZ && !window_hit(CB, cb_prev, WZ, lane)) {
       const double w = (double)WZ;
       const double var = (s2 - (s1 * s1) / w) / w;
       const double sdev = var > 0.0 ? sqrt(var) : 0.0;
@@ -296,12 +259,7 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
   for (int t0 = 0; t0 < T; t0 += WAVE) {
     const int t = t0 + lane;
     if (!any || t0 + WAVE <= from || t0 >= len) {   // no replayed candle in this step
-      if (t < T) {
-        st_out[t0] = BQ_RF_NO_FRAME;
-#pragma unroll
-        for (int k = 0; k < BQ_RF_NVALUES; ++k)
-          if (has_out(k)) vout[k][t0] = qnan();
-      }
+      if (t < T) O.no_frame(t0, BQ_RF_NO_FRAME);
       if (FEAT && any && t0 >= f0 && t0 < b0) {   // the step a replayed candle's windows reach back into
         double f[BQ_RF_NFEATURES];
         const bool in = t < T;
@@ -324,31 +282,25 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
     const RfStep cur = nxt;
     if (t0 + WAVE < len) nxt = load_step(t0 + WAVE);   // in flight during this step's arithmetic
     const bool valid = t >= from && t < len;
-    const RfKarg K = rf_karg();
+    const Karg<RfArgs> K = kernarg<RfArgs>();
     const auto& P = K->p;
 
     // :212: the frame's length, and isnull (NaN only) over the last min(5, rows) candles of the six columns
     const bool nul = t >= first && (cur.o != cur.o || cur.h != cur.h || cur.l != cur.l || cur.c != cur.c ||
                                     cur.rsi != cur.rsi || cur.v != cur.v);
     const uint64_t NB = __ballot(nul);
-    const bool short_frame = t + 1 - first < P.min_candles || rf_window_hit(NB, null_prev, RF_TAIL, lane);
+    const bool short_frame = t + 1 - first < P.min_candles || window_hit(NB, null_prev, RF_TAIL, lane);
     null_prev = NB;
 
     // the context and the symbol's snapshot entry at the candle's message
-    unsigned ci = K->ctx_T == 1 ? 0u : (unsigned)(t < T ? t : 0);
-    asm volatile("" : "+v"(ci));   // vector loads also where the context is one column
-    const unsigned ldc = (unsigned)K->ld_ctx;
-    const uint8_t* cokp = K->ctx_ok;
-    const double* ctxp = K->ctx;
-    const bool cok = cokp ? cokp[ci] != 0 : true;
-    const double trans = ctxp[ci], stress = ctxp[ldc + ci], regime = ctxp[2 * ldc + ci];
+    double cx[3];
+    const bool cok = ctx_load(K, ctx_index(K, t, T), cx);
+    const double trans = cx[0], stress = cx[1], regime = cx[2];
     bool sok = false;
     double satr = 0.0, sbbw = 0.0;
     int sreg = BQ_RF_NONE, strans = BQ_RF_NONE;
     if (K->sym_ok) {   // wave-uniform
-      const int64_t lds = K->ld_sym;
-      int64_t si = lds ? s * lds + (t < T ? t : 0) : s;
-      asm volatile("" : "+v"(si));
+      const int64_t si = sym_index(K, s, t, T);
       sok = K->sym_ok[si] != 0;
       satr = K->sym_atr[si];
       sbbw = K->sym_bbw[si];
@@ -387,10 +339,10 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
     const bool norange = range <= 0.0;
     const double closepos = (cur.c - cur.l) / range;
     const bool bull = !norange && cur.l <= cur.bbl * (1.0 + P.band_touch_tolerance) && cur.c > cur.o &&
-                      (rf_pymin(cur.o, cur.c) - cur.l) / range >= P.min_rejection_wick_frac &&
+                      (py_min(cur.o, cur.c) - cur.l) / range >= P.min_rejection_wick_frac &&
                       closepos >= P.long_close_position_min;
     const bool bear = !norange && cur.h >= cur.bbu * (1.0 - P.band_touch_tolerance) && cur.c < cur.o &&
-                      (cur.h - rf_pymax(cur.o, cur.c)) / range >= P.min_rejection_wick_frac &&
+                      (cur.h - py_max(cur.o, cur.c)) / range >= P.min_rejection_wick_frac &&
                       closepos <= P.short_close_position_max;
     // :180-194 (current_price is the candle's close)
     const bool lng = cur.c <= cur.bbm && cur.rsi <= P.long_rsi_max && z <= P.long_zscore_max && bull;
@@ -402,19 +354,19 @@ __global__ __launch_bounds__(RF_NT) void range_fade_kernel(const RfArgs A) {
     }
 
     // :264-274, unrounded, in the method's operation order
-    const double rpart = lng ? rf_pymax(0.0, (P.long_rsi_max - cur.rsi) / P.long_rsi_max)
-                             : rf_pymax(0.0, (cur.rsi - P.short_rsi_min) / 35.0);
-    const double score = ((1.0 + rf_pymin(fabs(z) / 3.0, 1.0) * 0.35) +
-                          rf_pymax(0.0, (P.adx_max - adx) / P.adx_max) * 0.25) + rpart * 0.25;
+    const double rpart = lng ? py_max(0.0, (P.long_rsi_max - cur.rsi) / P.long_rsi_max)
+                             : py_max(0.0, (cur.rsi - P.short_rsi_min) / 35.0);
+    const double score = ((1.0 + py_min(fabs(z) / 3.0, 1.0) * 0.35) +
+                          py_max(0.0, (P.adx_max - adx) / P.adx_max) * 0.25) + rpart * 0.25;
 
     if (t < T) {
-      st_out[t0] = (uint8_t)st;
+      O.st[t0] = (uint8_t)st;
       const bool emit = st == BQ_RF_EMIT;
-      if (has_out(BQ_RF_V_ADX)) vout[BQ_RF_V_ADX][t0] = (emit || st >= BQ_RF_ADX_TOO_HIGH) ? adx : qnan();
-      if (has_out(BQ_RF_V_ZSCORE)) vout[BQ_RF_V_ZSCORE][t0] = (emit || st >= BQ_RF_NO_SETUP) ? z : qnan();
-      if (has_out(BQ_RF_V_DIRECTION))
-        vout[BQ_RF_V_DIRECTION][t0] = emit ? (lng ? (double)BQ_DIR_LONG : (double)BQ_DIR_SHORT) : qnan();
-      if (has_out(BQ_RF_V_SCORE)) vout[BQ_RF_V_SCORE][t0] = emit ? score : qnan();
+      if (O.has(BQ_RF_V_ADX)) O.val[BQ_RF_V_ADX][t0] = (emit || st >= BQ_RF_ADX_TOO_HIGH) ? adx : qnan();
+      if (O.has(BQ_RF_V_ZSCORE)) O.val[BQ_RF_V_ZSCORE][t0] = (emit || st >= BQ_RF_NO_SETUP) ? z : qnan();
+      if (O.has(BQ_RF_V_DIRECTION))
+        O.val[BQ_RF_V_DIRECTION][t0] = emit ? (lng ? (double)BQ_DIR_LONG : (double)BQ_DIR_SHORT) : qnan();
+      if (O.has(BQ_RF_V_SCORE)) O.val[BQ_RF_V_SCORE][t0] = emit ? score : qnan();
     }
   }
 }
@@ -467,18 +419,16 @@ extern "C" int bq_range_fade_replay(const double* open, const double* high, cons
   if (params) A.p = *params;
   else bq_range_fade_default_params(&A.p);
   const bq_range_fade_params& p = A.p;
-  const double fin[] = {p.adx_max,          p.long_rsi_max,         p.short_rsi_min,
-                        p.long_zscore_max,  p.short_zscore_min,     p.band_touch_tolerance,
-                        p.max_market_stress, p.max_symbol_atr_pct,  p.max_symbol_bb_width,
-                        p.min_rejection_wick_frac, p.long_close_position_min, p.short_close_position_max};
-  for (double v : fin)
-    if (!(v - v == 0.0)) return BQ_EINVAL;
+  if (!all_finite({p.adx_max, p.long_rsi_max, p.short_rsi_min, p.long_zscore_max, p.short_zscore_min,
+                   p.band_touch_tolerance, p.max_market_stress, p.max_symbol_atr_pct, p.max_symbol_bb_width,
+                   p.min_rejection_wick_frac, p.long_close_position_min, p.short_close_position_max}))
+    return BQ_EINVAL;
   if (p.min_candles < 1 || p.adx_window < 1 || p.adx_window > BQ_RF_MAX_ADX_WINDOW || p.zscore_window < 1 ||
       p.zscore_window > BQ_RF_MAX_ZSCORE_WINDOW || p.adx_max == 0.0 || p.long_rsi_max == 0.0)
     return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t blocks = (S + RF_WPB - 1) / RF_WPB;
-  if (blocks > 0x7fffffff) return BQ_EINVAL;
+  int64_t blocks;
+  if (!replay_blocks(S, blocks)) return BQ_EINVAL;
   A.open = open;
   A.high = high;
   A.low = low;
@@ -510,11 +460,8 @@ extern "C" int bq_range_fade_replay(const double* open, const double* high, cons
   A.ctx_T = (int)ctx_T;
   A.ld_ctx = (int)ld_ctx;
   A.status = status;
-  for (int k = 0; k < BQ_RF_NVALUES; ++k) {
-    A.val[k] = values ? values[k] : nullptr;
-    A.omask |= A.val[k] ? 1 << k : 0;
-  }
-  const dim3 grid((unsigned)blocks), block(RF_NT);
+  replay_values(A.val, A.omask, values);
+  const dim3 grid((unsigned)blocks), block(RP_NT);
   hipStream_t st = (hipStream_t)stream;
   if (features) hipLaunchKernelGGL((range_fade_kernel<false>), grid, block, 0, st, A);
   else hipLaunchKernelGGL((range_fade_kernel<true>), grid, block, 0, st, A);

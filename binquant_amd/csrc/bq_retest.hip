@@ -6,8 +6,8 @@
 // whose frame is df.iloc[first_t[s]:t + 1], after the messages of all earlier
 // candles of the row (the semantics table: include/binquant_amd.h).
 //
-// retest_kernel: one wave per row, 64 candles per step (cooldown_kernel's
-// shape, bq_select.hip), every column one coalesced load per step.
+// retest_kernel: the wave-per-row replay mapping (bq_replay.h; from_t is taken
+// as given: candles before first_t are SHORT_HISTORY, not skipped).
 //   1. each lane forms its candle's state-independent values: frame long
 //      enough, leader, green reclaim, risk, the EMA arm of the support test,
 //      the t - 1 values (the neighbouring lane; lane 0 takes the previous
@@ -30,13 +30,10 @@
 // Domain: open_time strictly ascending within [first_t, lens): the
 // strategy_cooldowns check (:275-282) needs two messages with one open_time
 // and is not built.
-#include "bq_device.h"
+#include "bq_replay.h"
 #include "binquant_amd.h"
 
 namespace bq {
-
-constexpr int RT_NT = 256;            // threads: RT_NT / WAVE rows per workgroup
-constexpr int RT_WPB = RT_NT / WAVE;
 
 struct RetestArgs {
   const double *open, *high, *low, *close, *ema;
@@ -59,12 +56,13 @@ struct RetestStep {
   uint8_t lead, risk;
 };
 
-__global__ __launch_bounds__(RT_NT) void retest_kernel(const RetestArgs A) {
+__global__ __launch_bounds__(RP_NT) void retest_kernel(const RetestArgs A) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t s = (int64_t)blockIdx.x * RT_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int64_t s = replay_row_index();
   if (s >= A.S) return;   // whole wave
   const int T = A.T;
-  const int len = clamp_row(A.lens, s, T, T), first = clamp_row(A.first, s, 0, T), from = clamp_row(A.from, s, 0, T);
+  const ReplayRow R = replay_row<false>(A.lens, A.first, A.from, s, T);
+  const int len = R.len, first = R.first, from = R.from;
   const bq_retest_params P = A.p;
   const int L = P.breakout_lookback;
   const double sf = P.support_factor, pf = P.pullback_factor;
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(RT_NT) void retest_kernel(const RetestArgs A) {
   int64_t started = active ? A.st_started[s] : 0;
   double level = active ? A.st_level[s] : qnan();
 
-  const int b0 = from & ~(WAVE - 1);   // the first step that holds a replayed candle
+  const int b0 = R.b0();
   double h_prev_step = qnan();          // lane j: high[t0 - 64 + j]
   double c_h = qnan(), c_l = qnan(), c_c = qnan(), c_e = qnan();   // candle t0 - 1 (uniform)
   // one step's columns, candle tb + lane (NaN / 0 past the row's end)
@@ -106,7 +104,7 @@ __global__ __launch_bounds__(RT_NT) void retest_kernel(const RetestArgs A) {
   RetestStep nxt = {};
   for (int t0 = 0; t0 < T; t0 += WAVE) {
     const int t = t0 + lane;
-    if (from >= len || t0 + WAVE <= from || t0 >= len) {   // no replayed candle in this step
+    if (!R.any() || t0 + WAVE <= from || t0 >= len) {   // no replayed candle in this step
       if (t < T) {
         ev_out[t] = BQ_RT_NO_FRAME;
         if (dt_out) dt_out[t] = 0;
@@ -244,8 +242,8 @@ extern "C" int bq_retest_replay(const double* open, const double* high, const do
       A.p.breakout_lookback >= A.p.min_history || A.p.watch_ms < 0)
     return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t blocks = (S + RT_WPB - 1) / RT_WPB;
-  if (blocks > 0x7fffffff) return BQ_EINVAL;
+  int64_t blocks;
+  if (!replay_blocks(S, blocks)) return BQ_EINVAL;
   A.open = open;
   A.high = high;
   A.low = low;
@@ -269,6 +267,6 @@ extern "C" int bq_retest_replay(const double* open, const double* high, const do
   A.event = event;
   A.detail = detail;
   A.level = level;
-  hipLaunchKernelGGL(retest_kernel, dim3((unsigned)blocks), dim3(RT_NT), 0, (hipStream_t)stream, A);
+  hipLaunchKernelGGL(retest_kernel, dim3((unsigned)blocks), dim3(RP_NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }

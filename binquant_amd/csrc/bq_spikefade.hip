@@ -7,9 +7,7 @@
 // whose frame is df.iloc[first_t[s]:t + 1], after the messages of all earlier
 // candles of the row (the rule table: include/binquant_amd.h).
 //
-// spike_fade_kernel: retest_kernel's mapping (bq_retest.hip) — one wave per
-// row, 64 candles per step, every column one coalesced load per step, the
-// next step's columns loaded before this step's walk.
+// spike_fade_kernel: the wave-per-row replay mapping (bq_replay.h).
 //   1. the state (active, the spike's open_time / high / close, and its
 //      position p) is wave-uniform. Inside a replay the kernel knows p: it set
 //      it. A carried-in spike is looked up once per row before the first step,
@@ -38,13 +36,10 @@
 //
 // Domain: open_time strictly ascending within [first_t, lens), as for the
 // retest replay: the spike's position is unique.
-#include "bq_device.h"
+#include "bq_replay.h"
 #include "binquant_amd.h"
 
 namespace bq {
-
-constexpr int SF_NT = 256;            // threads: SF_NT / WAVE rows per workgroup
-constexpr int SF_WPB = SF_NT / WAVE;
 
 struct SpikeFadeArgs {
   const double *open, *high, *close;
@@ -66,13 +61,13 @@ struct SpikeFadeStep {
   uint8_t src, sm, fm;
 };
 
-__global__ __launch_bounds__(SF_NT) void spike_fade_kernel(const SpikeFadeArgs A) {
+__global__ __launch_bounds__(RP_NT) void spike_fade_kernel(const SpikeFadeArgs A) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t s = (int64_t)blockIdx.x * SF_WPB + __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int64_t s = replay_row_index();
   if (s >= A.S) return;   // whole wave
   const int T = A.T;
-  const int len = clamp_row(A.lens, s, T, T), first = clamp_row(A.first, s, 0, T), from0 = clamp_row(A.from, s, 0, T);
-  const int from = from0 > first ? from0 : first;   // a candle before first_t has an empty frame: no message
+  const ReplayRow R = replay_row(A.lens, A.first, A.from, s, T);
+  const int len = R.len, first = R.first, from = R.from;
   const int W = A.p.window_bars;
   const double ef = A.p.ext_factor;
   const double* __restrict__ op = A.open + s * A.ld_in;
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(SF_NT) void spike_fade_kernel(const SpikeFadeArgs A
   int p = 0;                // the pending spike's candle
   bool lost = false;        // a carried-in spike that is not in [first, from]
   bool ext_carry = false;   // a carried-in spike: some high in (p, from) extends beyond it
-  if (active && from < len) {
+  if (active && R.any()) {
     lost = true;
     for (int top = from; top >= first; top -= WAVE) {   // candles top, top - 1, ...: lane 0 is the newest
       const int u = top - lane;
@@ -113,7 +108,7 @@ __global__ __launch_bounds__(SF_NT) void spike_fade_kernel(const SpikeFadeArgs A
     }
   }
 
-  const int b0 = from & ~(WAVE - 1);   // the first step that holds a replayed candle
+  const int b0 = R.b0();
   // one step's columns, candle tb + lane (NaN / 0 past the row's end)
   auto load_step = [&](int tb) {
     const int u = tb + lane;
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(SF_NT) void spike_fade_kernel(const SpikeFadeArgs A
   SpikeFadeStep nxt = {};
   for (int t0 = 0; t0 < T; t0 += WAVE) {
     const int t = t0 + lane;
-    if (from >= len || t0 + WAVE <= from || t0 >= len) {   // no replayed candle in this step
+    if (!R.any() || t0 + WAVE <= from || t0 >= len) {   // no replayed candle in this step
       if (t < T) {
         ev_out[t] = BQ_FS_NO_FRAME;
         if (dt_out) dt_out[t] = 0;
@@ -243,11 +238,11 @@ extern "C" int bq_spike_fade_replay(const double* open, const double* high, cons
   SpikeFadeArgs A;
   if (params) A.p = *params;
   else bq_spike_fade_default_params(&A.p);
-  if (A.p.window_bars < 1 || A.p.window_bars > BQ_SPIKEFADE_MAX_WINDOW || !(A.p.ext_factor - A.p.ext_factor == 0.0))
+  if (A.p.window_bars < 1 || A.p.window_bars > BQ_SPIKEFADE_MAX_WINDOW || !all_finite({A.p.ext_factor}))
     return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t blocks = (S + SF_WPB - 1) / SF_WPB;
-  if (blocks > 0x7fffffff) return BQ_EINVAL;
+  int64_t blocks;
+  if (!replay_blocks(S, blocks)) return BQ_EINVAL;
   A.open = open;
   A.high = high;
   A.close = close;
@@ -272,6 +267,6 @@ extern "C" int bq_spike_fade_replay(const double* open, const double* high, cons
   A.event = event;
   A.detail = detail;
   A.bars = bars;
-  hipLaunchKernelGGL(spike_fade_kernel, dim3((unsigned)blocks), dim3(SF_NT), 0, (hipStream_t)stream, A);
+  hipLaunchKernelGGL(spike_fade_kernel, dim3((unsigned)blocks), dim3(RP_NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }

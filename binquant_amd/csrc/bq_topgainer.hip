@@ -67,11 +67,8 @@ struct TgArgs {
 
 enum { TG_VIN = 1, TG_VQV = 2, TG_VATR = 4, TG_VOUT = 8, TG_VBYTES = 16 };
 
-// Python's min(a, b) / max(a, b): the second argument wins only when the
+// py_min / py_max (bq_device.h): the second argument wins only when the
 // comparison holds, so a NaN first argument sticks and a NaN second is skipped
-__device__ __forceinline__ double py_min(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double py_max(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ bool tg_finite(double x) { return x - x == 0.0; }
 
 struct TgMax {   // Series.max(): NaN-skipping, NaN when nothing is left
   double m = qnan();
@@ -344,11 +341,11 @@ __global__ __launch_bounds__(TG::NT, 2) void top_gainer_kernel(const TgArgs A, i
       m = py_min(m, l[k]);
       m = py_min(m, v[k]);
       const bool f_inv = m <= 0.0;
-      const bool fin = tg_finite(c[k]) && tg_finite(o[k]) && tg_finite(h[k]) && tg_finite(l[k]) && tg_finite(v[k]) &&
-                       tg_finite(q[k]) && tg_finite(ph[k]) && tg_finite(r1[k]) && tg_finite(r2[k]) &&
-                       tg_finite(r6[k]) && tg_finite(ext[k]) && tg_finite(cap[k]) && tg_finite(cr[k]) &&
-                       tg_finite(vr[k]) && tg_finite(qvr[k]) && tg_finite(rp[k]) && tg_finite(uwf[k]) &&
-                       tg_finite(e20[k]) && tg_finite(e50[k]) && tg_finite(atr[k]);
+      const bool fin = is_finite(c[k]) && is_finite(o[k]) && is_finite(h[k]) && is_finite(l[k]) && is_finite(v[k]) &&
+                       is_finite(q[k]) && is_finite(ph[k]) && is_finite(r1[k]) && is_finite(r2[k]) &&
+                       is_finite(r6[k]) && is_finite(ext[k]) && is_finite(cap[k]) && is_finite(cr[k]) &&
+                       is_finite(vr[k]) && is_finite(qvr[k]) && is_finite(rp[k]) && is_finite(uwf[k]) &&
+                       is_finite(e20[k]) && is_finite(e50[k]) && is_finite(atr[k]);
       // _entry_allows (:163-187): the first failing check, selects from the last to the first
       int st = BQ_TGE_CONFIRMED;
       st = uwf[k] > P.max_upper_wick ? BQ_TGE_UPPER_WICK : st;

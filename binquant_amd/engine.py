@@ -1406,6 +1406,130 @@ def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
     return cols, ld
 
 
+# ---- the argument layer of the five replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
+# range_fade): each check raises the text the wrappers raised themselves, with the entry's name substituted
+
+def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None) -> dict:
+    """defaults overlaid with params; int_keys given: every other parameter is a finite float."""
+    bad = set(params) - set(defaults)
+    if bad:
+        raise ValueError(f"{entry}: unknown parameters {sorted(bad)} (known: {sorted(defaults)})")
+    par = {**defaults, **params}
+    if int_keys is not None:
+        for k, val in par.items():
+            if k not in int_keys and not math.isfinite(float(val)):
+                raise ValueError(f"{entry}: {k} must be finite, got {val}")
+    return par
+
+
+def _replay_struct(cls, par: dict, int_keys):
+    p = cls()
+    for k, val in par.items():
+        setattr(p, k, int(val) if k in int_keys else float(val))
+    return p
+
+
+def _replay_columns(entry: str, columns, known) -> None:
+    unknown = [k for k in columns if k not in known]
+    if unknown:
+        raise ValueError(f"{entry}: unknown columns {unknown} (known: {known})")
+
+
+def _replay_shape(c) -> tuple[int, int]:
+    if not isinstance(c, torch.Tensor) or c.dim() != 2:
+        raise ValueError("close: expected [S, T] with unit stride along T")
+    return c.shape
+
+
+def _replay_panels(pairs, S: int, T: int) -> None:
+    """(tensor, name) pairs: float64 [S, T]."""
+    for x, name in pairs:
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
+        if tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+
+
+def _replay_features(features, names) -> list:
+    """features: None (formed in the pass) or one tensor per name; as (tensor, name) pairs."""
+    if features is None:
+        return []
+    if len(features) != len(names):
+        raise ValueError(f"features: expected {names}")
+    return list(zip(features, names))
+
+
+def _replay_time(x, name: str, S: int, T: int) -> None:
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.int64 or tuple(x.shape) != (S, T):
+        raise ValueError(f"{name}: expected an int64 tensor of shape {(S, T)}")
+
+
+def _replay_ctx(ctx, ctx_ok, rows, T: int):
+    """ctx float64 [len(rows), Tc], Tc 1 or T, and ctx_ok [Tc] or None. Returns
+    (ctx, ctx_ok, Tc, ld_ctx) with unit stride along Tc."""
+    n = len(rows)
+    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
+            or ctx.shape[0] != n or ctx.shape[1] not in (1, T)):
+        raise ValueError(f"ctx: expected a float64 tensor of shape {(n, 1)} or {(n, T)} (rows {rows})")
+    Tc = int(ctx.shape[1])
+    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
+                               or tuple(ctx_ok.shape) != (Tc,)):
+        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
+    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
+        ctx = ctx.contiguous()
+    if ctx_ok is not None and not ctx_ok.is_contiguous():
+        ctx_ok = ctx_ok.contiguous()
+    return ctx, ctx_ok, Tc, int(ctx.stride(0))
+
+
+def _replay_sym(sym, spec, S: int, T: int):
+    """sym: None or one tensor per (name, dtypes) of spec, all [S] or all [S, T].
+    Returns (the tensors, contiguous, or a None per entry; ld_sym: T or 0)."""
+    if sym is None:
+        return [None] * len(spec), 0
+    if len(sym) != len(spec):
+        raise ValueError(f"sym: expected {tuple(n for n, _ in spec)}")
+    shp = tuple(getattr(sym[0], "shape", ()))
+    if shp not in ((S,), (S, T)):
+        raise ValueError(f"sym: expected tensors of shape {(S,)} or {(S, T)}")
+    for x, (name, dts) in zip(sym, spec):
+        if not isinstance(x, torch.Tensor) or x.dtype not in dts or tuple(x.shape) != shp:
+            raise ValueError(f"sym.{name}: expected a {dts[0]} tensor of shape {shp}")
+    return [x.contiguous() for x in sym], (T if len(shp) == 2 else 0)
+
+
+def _replay_state(state, names, dtypes, S: int):
+    """state: None or one contiguous [S] tensor per name. Returns them, or a None per name."""
+    if state is None:
+        return (None,) * len(names)
+    if len(state) != len(names):
+        raise ValueError(f"state: expected ({', '.join(names)})")
+    for x, name, dt in zip(state, names, dtypes):
+        if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
+            raise ValueError(f"state.{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    return tuple(state)
+
+
+def _replay_rows(lens, first_t, from_t, S: int, dev=None):
+    """lens / first_t / from_t: gated on the host (dev None), or as int64 [S] on dev."""
+    rows = zip((lens, first_t, from_t), ("lens", "first_t", "from_t"))
+    if dev is None:
+        return tuple(_gate_rows(v, name, S) for v, name in rows)
+    return tuple(_check_lens(v, S, dev) for v, _ in rows)
+
+
+def _replay_on_device(label: str, tensors) -> None:
+    if not all(x.is_cuda for x in tensors if x is not None):
+        raise ValueError(f"{label}: expected CUDA tensors (no CPU path)")
+
+
+def _replay_outputs(columns, known, S: int, T: int, dev):
+    """status uint8 [S, T], {name: float64 [S, T]} for columns, and the values' pointer array in `known` order."""
+    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
+    return status, outs, _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in known])
+
+
 @device_entry
 def impulse_rider(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Tensor, atr: torch.Tensor,
                   open_time: torch.Tensor, bench_ts: torch.Tensor, bench_close: torch.Tensor, *, first_t=None,
@@ -1710,56 +1834,35 @@ def retest_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Te
     level float64) [S] tensors, updated in place. Returns (event uint8,
     detail uint8 or None, level float64 or None), each [S, T] (_lib.BQ_RT_*).
     params: RETEST_DEFAULTS' keys (the two factors formed in Python floats)."""
-    bad = set(params) - set(RETEST_DEFAULTS)
-    if bad:
-        raise ValueError(f"retest_replay: unknown parameters {sorted(bad)} (known: {sorted(RETEST_DEFAULTS)})")
-    par = {**RETEST_DEFAULTS, **params}
+    par = _replay_params("retest_replay", RETEST_DEFAULTS, params)
     L, mh = int(par["breakout_lookback"]), int(par["min_history"])
     if not 1 <= L <= _lib.RETEST_MAX_LOOKBACK or L >= mh:
         raise ValueError(f"retest_replay: breakout_lookback must be in 1..{_lib.RETEST_MAX_LOOKBACK} and below "
                          f"min_history ({mh}), got {L}")
     if int(par["watch_ms"]) < 0:
         raise ValueError("retest_replay: watch_ms must be >= 0")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
-    for x, name in ((o, "open"), (h, "high"), (l, "low"), (c, "close"), (ema, "ema")):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
-        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
-    for x, name in ((leader, "leader"), (risk_ok, "risk_ok")):
-        if x is None and name == "risk_ok":
-            continue
+    S, T = _replay_shape(c)
+    px = ((o, "open"), (h, "high"), (l, "low"), (c, "close"), (ema, "ema"))
+    _replay_panels(px, S, T)
+    _replay_time(open_time, "open_time", S, T)
+    flags = [leader] if risk_ok is None else [leader, risk_ok]
+    for x, name in zip(flags, ("leader", "risk_ok")):
         if not isinstance(x, torch.Tensor) or x.dtype != torch.bool or tuple(x.shape) != (S, T):
             raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)}")
-    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
-        _gate_rows(from_t, "from_t", S)
-    if state is not None:
-        if len(state) != 3:
-            raise ValueError("state: expected (active, started, level)")
-        for x, name, dt in zip(state, ("state.active", "state.started", "state.level"),
-                               (torch.uint8, torch.int64, torch.float64)):
-            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
-    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in ((o, "open"), (h, "high"), (l, "low"), (c, "close"),
-                                                                 (ema, "ema"))])
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    sa, ss, sl = _replay_state(state, ("active", "started", "level"), (torch.uint8, torch.int64, torch.float64), S)
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in px])
     ts = _check_ts(open_time, "open_time")
-    flags = [leader] if risk_ok is None else [leader, risk_ok]
-    if not all(x.is_cuda for x in flags + list(state or ())):
-        raise ValueError("leader / risk_ok / state: expected CUDA tensors (no CPU path)")
+    _replay_on_device("leader / risk_ok / state", flags + [sa, ss, sl])
     if any(f.shape[1] > 1 and f.stride(1) != 1 for f in flags):
         flags = [f.contiguous() for f in flags]
     flags, ld_b = _common_pitch(flags)
     dev = c.device
-    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
     p = _lib.BqRetestParams(int(par["watch_ms"]), mh, L, float(par["support_factor"]), float(par["pullback_factor"]))
     event = torch.empty((S, T), dtype=torch.uint8, device=dev)
     det = torch.empty((S, T), dtype=torch.uint8, device=dev) if detail else None
     lvl = torch.empty((S, T), dtype=torch.float64, device=dev) if level else None
-    sa, ss, sl = state if state is not None else (None, None, None)
     st = _lib.load().bq_retest_replay(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), ld_in,
                                       _ptr(ts), T, _ptr(flags[0]), _ptr(flags[1] if risk_ok is not None else None),
                                       ld_b, _ptr(lens), _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(sa),
@@ -1792,25 +1895,16 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
     (event uint8, detail uint8 or None, bars uint8 or None), each [S, T]
     (_lib.BQ_FS_*). params: SPIKE_FADE_DEFAULTS' keys (ext_factor formed in
     Python floats)."""
-    bad = set(params) - set(SPIKE_FADE_DEFAULTS)
-    if bad:
-        raise ValueError(f"spike_fade_replay: unknown parameters {sorted(bad)} (known: {sorted(SPIKE_FADE_DEFAULTS)})")
-    par = {**SPIKE_FADE_DEFAULTS, **params}
+    par = _replay_params("spike_fade_replay", SPIKE_FADE_DEFAULTS, params)
     W, ef = int(par["window_bars"]), float(par["ext_factor"])
     if not 1 <= W <= _lib.SPIKEFADE_MAX_WINDOW:
         raise ValueError(f"spike_fade_replay: window_bars must be in 1..{_lib.SPIKEFADE_MAX_WINDOW}, got {W}")
     if not math.isfinite(ef):
         raise ValueError(f"spike_fade_replay: ext_factor must be finite, got {ef}")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
-    for x, name in ((o, "open"), (h, "high"), (c, "close")):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
-        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
+    S, T = _replay_shape(c)
+    px = ((o, "open"), (h, "high"), (c, "close"))
+    _replay_panels(px, S, T)
+    _replay_time(open_time, "open_time", S, T)
     if not isinstance(source_ok, torch.Tensor) or source_ok.dtype != torch.bool or tuple(source_ok.shape) != (S, T):
         raise ValueError(f"source_ok: expected a bool tensor of shape {(S, T)}")
     for m, name in ((src_market, "src_market"), (fail_market, "fail_market")):
@@ -1820,20 +1914,13 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
     shared = [m.dim() == 1 for m in (src_market, fail_market) if m is not None]
     if len(set(shared)) > 1:
         raise ValueError("src_market / fail_market: both [S, T] or both [T] (they share one row stride)")
-    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
-        _gate_rows(from_t, "from_t", S)
-    if state is not None:
-        if len(state) != 4:
-            raise ValueError("state: expected (active, open_time, high, close)")
-        for x, name, dt in zip(state, ("state.active", "state.open_time", "state.high", "state.close"),
-                               (torch.uint8, torch.int64, torch.float64, torch.float64)):
-            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
-    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in ((o, "open"), (h, "high"), (c, "close"))])
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    sa, so, sh, sc = _replay_state(state, ("active", "open_time", "high", "close"),
+                                   (torch.uint8, torch.int64, torch.float64, torch.float64), S)
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in px])
     ts = _check_ts(open_time, "open_time")
     masks = [m for m in (src_market, fail_market) if m is not None]
-    if not all(x.is_cuda for x in [source_ok] + masks + list(state or ())):
-        raise ValueError("source_ok / src_market / fail_market / state: expected CUDA tensors (no CPU path)")
+    _replay_on_device("source_ok / src_market / fail_market / state", [source_ok] + masks + [sa, so, sh, sc])
     if T > 1 and source_ok.stride(1) != 1:
         source_ok = source_ok.contiguous()
     ld_m = T
@@ -1847,12 +1934,11 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
     sm = next(masks) if src_market is not None else None
     fm = next(masks) if fail_market is not None else None
     dev = c.device
-    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
     p = _lib.BqSpikeFadeParams(W, ef)
     event = torch.empty((S, T), dtype=torch.uint8, device=dev)
     det = torch.empty((S, T), dtype=torch.uint8, device=dev) if detail else None
     brs = torch.empty((S, T), dtype=torch.uint8, device=dev) if bars else None
-    sa, so, sh, sc = state if state is not None else (None, None, None, None)
     st = _lib.load().bq_spike_fade_replay(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ld_in, _ptr(ts), T,
                                           _ptr(source_ok), _row_stride(source_ok), _ptr(sm), _ptr(fm), ld_m,
                                           _ptr(lens), _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(sa),
@@ -1893,83 +1979,43 @@ def price_tracker_replay(c: torch.Tensor, rsi: torch.Tensor, macd: torch.Tensor,
     None, {name: float64 [S, T]} for `columns`, a subset of _lib.PT_VALUES,
     NaN where the method did not reach them). params: PRICE_TRACKER_DEFAULTS'
     keys (cooldown_ms 0: strategy_cooldowns is None)."""
-    bad = set(params) - set(PRICE_TRACKER_DEFAULTS)
-    if bad:
-        raise ValueError(f"price_tracker_replay: unknown parameters {sorted(bad)} "
-                         f"(known: {sorted(PRICE_TRACKER_DEFAULTS)})")
-    par = {**PRICE_TRACKER_DEFAULTS, **params}
-    for k, val in par.items():
-        if k not in _PT_INT_PARAMS and not math.isfinite(float(val)):
-            raise ValueError(f"price_tracker_replay: {k} must be finite, got {val}")
+    par = _replay_params("price_tracker_replay", PRICE_TRACKER_DEFAULTS, params, _PT_INT_PARAMS)
     if int(par["min_history"]) < 1 or not 1 <= int(par["tail_rows"]) <= _lib.PT_MAX_TAIL_ROWS:
         raise ValueError(f"price_tracker_replay: min_history >= 1 and tail_rows in 1..{_lib.PT_MAX_TAIL_ROWS}")
     if int(par["span_fast"]) < 1 or int(par["span_slow"]) < 1 or int(par["cooldown_ms"]) < 0:
         raise ValueError("price_tracker_replay: spans must be >= 1 and cooldown_ms >= 0")
     if float(par["rsi_max"]) == 0.0 or float(par["mfi_max"]) == 0.0:
         raise ValueError("price_tracker_replay: rsi_max and mfi_max divide local_score's terms: not 0")
-    unknown = [k for k in columns if k not in _lib.PT_VALUES]
-    if unknown:
-        raise ValueError(f"price_tracker_replay: unknown columns {unknown} (known: {_lib.PT_VALUES})")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
+    _replay_columns("price_tracker_replay", columns, _lib.PT_VALUES)
+    S, T = _replay_shape(c)
     px = [(c, "close")] + [(x, n) for x, n in ((h, "high"), (l, "low"), (v, "volume")) if x is not None]
     ind = [(rsi, "rsi"), (macd, "macd"), (mfi, "mfi")]
     opt = [(trend_score, "trend_score")] if trend_score is not None else []
-    for x, name in px + ind + opt:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    if not isinstance(close_time, torch.Tensor) or close_time.dtype != torch.int64 or tuple(close_time.shape) != (S, T):
-        raise ValueError(f"close_time: expected an int64 tensor of shape {(S, T)}")
+    _replay_panels(px + ind + opt, S, T)
+    _replay_time(close_time, "close_time", S, T)
     if (not isinstance(symbol_rs, torch.Tensor) or symbol_rs.dtype != torch.float64
             or tuple(symbol_rs.shape) not in ((S,), (S, T))):
         raise ValueError(f"symbol_rs: expected a float64 tensor of shape {(S,)} or {(S, T)}")
-    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
-            or ctx.shape[0] != len(_lib.PT_CTX_ROWS) or ctx.shape[1] not in (1, T)):
-        raise ValueError(f"ctx: expected a float64 tensor of shape (4, 1) or {(4, T)} (rows {_lib.PT_CTX_ROWS})")
-    Tc = int(ctx.shape[1])
-    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
-                               or tuple(ctx_ok.shape) != (Tc,)):
-        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
-    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
-        _gate_rows(from_t, "from_t", S)
-    if state is not None:
-        if len(state) != 2:
-            raise ValueError("state: expected (has, last_close_time)")
-        for x, name, dt in zip(state, ("state.has", "state.last_close_time"), (torch.uint8, torch.int64)):
-            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    ctx, ctx_ok, Tc, ld_ctx = _replay_ctx(ctx, ctx_ok, _lib.PT_CTX_ROWS, T)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    sh, sl = _replay_state(state, ("has", "last_close_time"), (torch.uint8, torch.int64), S)
     pxs, ld_px = _common_pitch([_check_panel(x, n) for x, n in px])
     inds, ld_ind = _common_pitch([_check_panel(x, n) for x, n in ind])
     tr = _check_panel(trend_score, "trend_score") if trend_score is not None else None
     ct = _check_ts(close_time, "close_time")
-    others = [symbol_rs, ctx] + ([ctx_ok] if ctx_ok is not None else []) + list(state or ())
-    if not all(x.is_cuda for x in others):
-        raise ValueError("symbol_rs / ctx / ctx_ok / state: expected CUDA tensors (no CPU path)")
+    _replay_on_device("symbol_rs / ctx / ctx_ok / state", [symbol_rs, ctx, ctx_ok, sh, sl])
     if symbol_rs.dim() == 2:
         symbol_rs = _check_panel(symbol_rs, "symbol_rs")
         ld_rs = _row_stride(symbol_rs)
     else:
         symbol_rs, ld_rs = symbol_rs.contiguous(), 0
-    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
-        ctx = ctx.contiguous()
-    ld_ctx = int(ctx.stride(0))
-    if ctx_ok is not None and not ctx_ok.is_contiguous():
-        ctx_ok = ctx_ok.contiguous()
     cc, rest = pxs[0], iter(pxs[1:])
     hh, ll, vv = (next(rest) if x is not None else None for x in (h, l, v))
     dev = c.device
-    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
-    p = _lib.BqPriceTrackerParams()
-    for k, val in par.items():
-        setattr(p, k, int(val) if k in _PT_INT_PARAMS else float(val))
-    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqPriceTrackerParams, par, _PT_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.PT_VALUES, S, T, dev)
     det = torch.empty((S, T), dtype=torch.uint8, device=dev) if detail else None
-    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
-    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.PT_VALUES])
-    sh, sl = state if state is not None else (None, None)
     st = _lib.load().bq_price_tracker_replay(
         _ptr(cc), _ptr(hh), _ptr(ll), _ptr(vv), ld_px, _ptr(inds[0]), _ptr(inds[1]), _ptr(inds[2]), ld_ind, _ptr(ct), T,
         _ptr(tr), _row_stride(tr) if tr is not None else T, _ptr(symbol_rs), ld_rs, _ptr(ctx), ld_ctx, _ptr(ctx_ok), Tc,
@@ -2013,93 +2059,33 @@ def mean_reversion_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: 
     [S, T] (_lib.MR_REASONS' indices), {name: float64 [S, T]} for `columns`, a
     subset of _lib.MR_VALUES, NaN where the method did not reach them).
     params: MEAN_REVERSION_DEFAULTS' keys."""
-    bad = set(params) - set(MEAN_REVERSION_DEFAULTS)
-    if bad:
-        raise ValueError(f"mean_reversion_replay: unknown parameters {sorted(bad)} "
-                         f"(known: {sorted(MEAN_REVERSION_DEFAULTS)})")
-    par = {**MEAN_REVERSION_DEFAULTS, **params}
-    for k, val in par.items():
-        if k not in _MR_INT_PARAMS and not math.isfinite(float(val)):
-            raise ValueError(f"mean_reversion_replay: {k} must be finite, got {val}")
+    par = _replay_params("mean_reversion_replay", MEAN_REVERSION_DEFAULTS, params, _MR_INT_PARAMS)
     if int(par["rsi_window"]) < 1 or int(par["ema_fast"]) < 1 or int(par["ema_slow"]) < 1:
         raise ValueError("mean_reversion_replay: rsi_window and the spans must be >= 1")
     if not all(1 <= int(par[k]) <= _lib.MR_MAX_WINDOW for k in ("volume_ma_window", "atr_ma_window")):
         raise ValueError(f"mean_reversion_replay: volume_ma_window and atr_ma_window in 1..{_lib.MR_MAX_WINDOW}")
     if float(par["rsi_short_min"]) == 100.0:
         raise ValueError("mean_reversion_replay: 100 - rsi_short_min divides the score: not 100")
-    unknown = [k for k in columns if k not in _lib.MR_VALUES]
-    if unknown:
-        raise ValueError(f"mean_reversion_replay: unknown columns {unknown} (known: {_lib.MR_VALUES})")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
+    _replay_columns("mean_reversion_replay", columns, _lib.MR_VALUES)
+    S, T = _replay_shape(c)
     px = [(o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume")]
-    if features is not None:
-        if len(features) != _lib.MR_NFEATURES:
-            raise ValueError(f"features: expected {_lib.MR_VALUES[:_lib.MR_NFEATURES]}")
-        ft = list(zip(features, _lib.MR_VALUES))
-    else:
-        ft = []
-    for x, name in px + [(atr, "atr"), (bb_upper, "bb_upper")] + ft:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
-        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
-    nctx = len(_lib.MR_CTX_ROWS)
-    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
-            or ctx.shape[0] != nctx or ctx.shape[1] not in (1, T)):
-        raise ValueError(f"ctx: expected a float64 tensor of shape {(nctx, 1)} or {(nctx, T)} "
-                         f"(rows {_lib.MR_CTX_ROWS})")
-    Tc = int(ctx.shape[1])
-    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
-                               or tuple(ctx_ok.shape) != (Tc,)):
-        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
-    if sym is not None:
-        if len(sym) != len(_MR_SYM):
-            raise ValueError(f"sym: expected {tuple(n for n, _ in _MR_SYM)}")
-        shp = tuple(getattr(sym[0], "shape", ()))
-        if shp not in ((S,), (S, T)):
-            raise ValueError(f"sym: expected tensors of shape {(S,)} or {(S, T)}")
-        for x, (name, dts) in zip(sym, _MR_SYM):
-            if not isinstance(x, torch.Tensor) or x.dtype not in dts or tuple(x.shape) != shp:
-                raise ValueError(f"sym.{name}: expected a {dts[0]} tensor of shape {shp}")
-    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
-        _gate_rows(from_t, "from_t", S)
-    if state is not None:
-        if len(state) != 2:
-            raise ValueError("state: expected (has, last_open_time)")
-        for x, name, dt in zip(state, ("state.has", "state.last_open_time"), (torch.uint8, torch.int64)):
-            if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != (S,) or not x.is_contiguous():
-                raise ValueError(f"{name}: expected a contiguous {dt} tensor of shape {(S,)}")
+    ft = _replay_features(features, _lib.MR_VALUES[:_lib.MR_NFEATURES])
+    _replay_panels(px + [(atr, "atr"), (bb_upper, "bb_upper")] + ft, S, T)
+    _replay_time(open_time, "open_time", S, T)
+    ctx, ctx_ok, Tc, ld_ctx = _replay_ctx(ctx, ctx_ok, _lib.MR_CTX_ROWS, T)
+    sy, ld_sym = _replay_sym(sym, _MR_SYM, S, T)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    sh, sl = _replay_state(state, ("has", "last_open_time"), (torch.uint8, torch.int64), S)
     pxs, ld_px = _common_pitch([_check_panel(x, n) for x, n in px])
     atr, bb_upper = _check_panel(atr, "atr"), _check_panel(bb_upper, "bb_upper")
     fts, ld_ft = _common_pitch([_check_panel(x, n) for x, n in ft]) if ft else ([], T)
     ot = _check_ts(open_time, "open_time")
-    others = [ctx] + ([ctx_ok] if ctx_ok is not None else []) + list(sym or ()) + list(state or ())
-    if not all(x.is_cuda for x in others):
-        raise ValueError("ctx / ctx_ok / sym / state: expected CUDA tensors (no CPU path)")
-    ld_sym = 0
-    if sym is not None:
-        sym = [x.contiguous() for x in sym]
-        ld_sym = T if sym[0].dim() == 2 else 0
-    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
-        ctx = ctx.contiguous()
-    ld_ctx = int(ctx.stride(0))
-    if ctx_ok is not None and not ctx_ok.is_contiguous():
-        ctx_ok = ctx_ok.contiguous()
+    _replay_on_device("ctx / ctx_ok / sym / state", [ctx, ctx_ok, *sy, sh, sl])
     dev = c.device
-    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
-    p = _lib.BqMeanReversionParams()
-    for k, val in par.items():
-        setattr(p, k, int(val) if k in _MR_INT_PARAMS else float(val))
-    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
-    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
-    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.MR_VALUES])
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqMeanReversionParams, par, _MR_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.MR_VALUES, S, T, dev)
     feats = _lib.ptr_array([x.data_ptr() for x in fts]) if fts else None
-    sh, sl = state if state is not None else (None, None)
-    sy = sym if sym is not None else [None] * len(_MR_SYM)
     st = _lib.load().bq_mean_reversion_replay(
         _ptr(pxs[0]), _ptr(pxs[1]), _ptr(pxs[2]), _ptr(pxs[3]), _ptr(pxs[4]), ld_px, _ptr(atr), _row_stride(atr),
         _ptr(bb_upper), _row_stride(bb_upper), _ptr(ot), T, feats, ld_ft, _ptr(ctx), ld_ctx, _ptr(ctx_ok), Tc,
@@ -2144,14 +2130,7 @@ def range_fade_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torc
     float64 tensors. Returns (status uint8 [S, T] (_lib.RF_REASONS' indices),
     {name: float64 [S, T]} for `columns`, a subset of _lib.RF_VALUES, NaN where
     the method did not reach them). params: RANGE_FADE_DEFAULTS' keys."""
-    bad = set(params) - set(RANGE_FADE_DEFAULTS)
-    if bad:
-        raise ValueError(f"range_fade_replay: unknown parameters {sorted(bad)} "
-                         f"(known: {sorted(RANGE_FADE_DEFAULTS)})")
-    par = {**RANGE_FADE_DEFAULTS, **params}
-    for k, val in par.items():
-        if k not in _RF_INT_PARAMS and not math.isfinite(float(val)):
-            raise ValueError(f"range_fade_replay: {k} must be finite, got {val}")
+    par = _replay_params("range_fade_replay", RANGE_FADE_DEFAULTS, params, _RF_INT_PARAMS)
     if int(par["min_candles"]) < 1:
         raise ValueError("range_fade_replay: min_candles must be >= 1")
     if not 1 <= int(par["adx_window"]) <= _lib.RF_MAX_ADX_WINDOW:
@@ -2160,71 +2139,25 @@ def range_fade_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torc
         raise ValueError(f"range_fade_replay: zscore_window in 1..{_lib.RF_MAX_ZSCORE_WINDOW}")
     if float(par["adx_max"]) == 0.0 or float(par["long_rsi_max"]) == 0.0:
         raise ValueError("range_fade_replay: adx_max and long_rsi_max divide the score: not 0")
-    unknown = [k for k in columns if k not in _lib.RF_VALUES]
-    if unknown:
-        raise ValueError(f"range_fade_replay: unknown columns {unknown} (known: {_lib.RF_VALUES})")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
+    _replay_columns("range_fade_replay", columns, _lib.RF_VALUES)
+    S, T = _replay_shape(c)
     px = [(o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume")]
     bb = [(bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower")]
-    if features is not None:
-        if len(features) != _lib.RF_NFEATURES:
-            raise ValueError(f"features: expected {_lib.RF_VALUES[:_lib.RF_NFEATURES]}")
-        ft = list(zip(features, _lib.RF_VALUES))
-    else:
-        ft = []
-    for x, name in px + [(rsi, "rsi")] + bb + ft:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    nctx = len(_lib.RF_CTX_ROWS)
-    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
-            or ctx.shape[0] != nctx or ctx.shape[1] not in (1, T)):
-        raise ValueError(f"ctx: expected a float64 tensor of shape {(nctx, 1)} or {(nctx, T)} "
-                         f"(rows {_lib.RF_CTX_ROWS})")
-    Tc = int(ctx.shape[1])
-    if ctx_ok is not None and (not isinstance(ctx_ok, torch.Tensor) or ctx_ok.dtype not in (torch.bool, torch.uint8)
-                               or tuple(ctx_ok.shape) != (Tc,)):
-        raise ValueError(f"ctx_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
-    if sym is not None:
-        if len(sym) != len(_RF_SYM):
-            raise ValueError(f"sym: expected {tuple(n for n, _ in _RF_SYM)}")
-        shp = tuple(getattr(sym[0], "shape", ()))
-        if shp not in ((S,), (S, T)):
-            raise ValueError(f"sym: expected tensors of shape {(S,)} or {(S, T)}")
-        for x, (name, dts) in zip(sym, _RF_SYM):
-            if not isinstance(x, torch.Tensor) or x.dtype not in dts or tuple(x.shape) != shp:
-                raise ValueError(f"sym.{name}: expected a {dts[0]} tensor of shape {shp}")
-    lens, first_t, from_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S), \
-        _gate_rows(from_t, "from_t", S)
+    ft = _replay_features(features, _lib.RF_VALUES[:_lib.RF_NFEATURES])
+    _replay_panels(px + [(rsi, "rsi")] + bb + ft, S, T)
+    ctx, ctx_ok, Tc, ld_ctx = _replay_ctx(ctx, ctx_ok, _lib.RF_CTX_ROWS, T)
+    sy, ld_sym = _replay_sym(sym, _RF_SYM, S, T)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
     pxs, ld_px = _common_pitch([_check_panel(x, n) for x, n in px])
     rsi = _check_panel(rsi, "rsi")
     bbs, ld_bb = _common_pitch([_check_panel(x, n) for x, n in bb])
     fts, ld_ft = _common_pitch([_check_panel(x, n) for x, n in ft]) if ft else ([], T)
-    others = [ctx] + ([ctx_ok] if ctx_ok is not None else []) + list(sym or ())
-    if not all(x.is_cuda for x in others):
-        raise ValueError("ctx / ctx_ok / sym: expected CUDA tensors (no CPU path)")
-    ld_sym = 0
-    if sym is not None:
-        sym = [x.contiguous() for x in sym]
-        ld_sym = T if sym[0].dim() == 2 else 0
-    if (Tc > 1 and ctx.stride(1) != 1) or ctx.stride(0) < Tc:
-        ctx = ctx.contiguous()
-    ld_ctx = int(ctx.stride(0))
-    if ctx_ok is not None and not ctx_ok.is_contiguous():
-        ctx_ok = ctx_ok.contiguous()
+    _replay_on_device("ctx / ctx_ok / sym", [ctx, ctx_ok, *sy])
     dev = c.device
-    lens, first_t, from_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev), _check_lens(from_t, S, dev)
-    p = _lib.BqRangeFadeParams()
-    for k, val in par.items():
-        setattr(p, k, int(val) if k in _RF_INT_PARAMS else float(val))
-    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
-    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
-    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.RF_VALUES])
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqRangeFadeParams, par, _RF_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.RF_VALUES, S, T, dev)
     feats = _lib.ptr_array([x.data_ptr() for x in fts]) if fts else None
-    sy = sym if sym is not None else [None] * len(_RF_SYM)
     st = _lib.load().bq_range_fade_replay(
         _ptr(pxs[0]), _ptr(pxs[1]), _ptr(pxs[2]), _ptr(pxs[3]), _ptr(pxs[4]), ld_px, _ptr(rsi), _row_stride(rsi),
         _ptr(bbs[0]), _ptr(bbs[1]), _ptr(bbs[2]), ld_bb, feats, ld_ft, _ptr(ctx), ld_ctx, _ptr(ctx_ok), Tc,

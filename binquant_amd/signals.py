@@ -799,6 +799,16 @@ class MeanReversionState:
         return self.has, self.last_open_time
 
 
+def _pick(d, keys, what: str):
+    """A {name: tensor} argument (`what`: "sym" / "features") as the tuple in `keys` order; None stays None."""
+    if d is None:
+        return None
+    missing = [k for k in keys if k not in d]
+    if missing:
+        raise ValueError(f"{what}: missing {missing} (expected {keys})")
+    return tuple(d[k] for k in keys)
+
+
 def mean_reversion_fade_entry(o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_ok=None, *, sym=None, features=None,
                               state: MeanReversionState | None = None, first_t=None, lens=None, from_t=None,
                               columns=MR_VALUES, **params):
@@ -826,16 +836,7 @@ def mean_reversion_fade_entry(o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_
     and score are unrounded: round_numbers(.., 4) / round(.., 4), the FUTURES
     and ATR-column checks, the message text and the dispatch stay host
     steps."""
-    if sym is not None:
-        missing = [k for k in MR_SYM_KEYS if k not in sym]
-        if missing:
-            raise ValueError(f"sym: missing {missing} (expected {MR_SYM_KEYS})")
-        sym = tuple(sym[k] for k in MR_SYM_KEYS)
-    if features is not None:
-        missing = [k for k in MR_FEATURES if k not in features]
-        if missing:
-            raise ValueError(f"features: missing {missing} (expected {MR_FEATURES})")
-        features = tuple(features[k] for k in MR_FEATURES)
+    sym, features = _pick(sym, MR_SYM_KEYS, "sym"), _pick(features, MR_FEATURES, "features")
     status, vals = engine.mean_reversion_replay(
         o, h, l, c, v, atr, bb_upper, open_time, ctx, ctx_ok, sym=sym, features=features,
         state=state.tensors() if state is not None else None, first_t=first_t, lens=lens, from_t=from_t,
@@ -886,16 +887,7 @@ def range_fade_entry(o, h, l, c, v, rsi, bb_upper, bb_mid, bb_lower, ctx, ctx_ok
     no_bb_rsi_rejection_setup on, direction (RF_LONG / RF_SHORT) and score
     (local_score, unrounded) where it emits}. The rounding of the bands, the
     message text and the dispatch stay host steps."""
-    if sym is not None:
-        missing = [k for k in RF_SYM_KEYS if k not in sym]
-        if missing:
-            raise ValueError(f"sym: missing {missing} (expected {RF_SYM_KEYS})")
-        sym = tuple(sym[k] for k in RF_SYM_KEYS)
-    if features is not None:
-        missing = [k for k in RF_FEATURES if k not in features]
-        if missing:
-            raise ValueError(f"features: missing {missing} (expected {RF_FEATURES})")
-        features = tuple(features[k] for k in RF_FEATURES)
+    sym, features = _pick(sym, RF_SYM_KEYS, "sym"), _pick(features, RF_FEATURES, "features")
     status, vals = engine.range_fade_replay(
         o, h, l, c, v, rsi, bb_upper, bb_mid, bb_lower, ctx, ctx_ok, sym=sym, features=features, first_t=first_t,
         lens=lens, from_t=from_t, columns=columns, **params)
