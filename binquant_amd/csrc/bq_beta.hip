@@ -10,7 +10,10 @@
 //   cov  = (mean_xy - mean_x * mean_y) * (n / (n - 1))
 //   beta = cov / var_y            (var_y == 0 -> NaN: var.replace(0, nan))
 //   corr = cov / (var_x * var_y) ** 0.5                 (roll_var, ddof 1)
-// NaN where the window is incomplete (t < window).
+// NaN where the window is incomplete (t < window). A missing (NaN) or zero
+// close drops its pairs as the reference's dropna does: the window is the
+// last `window` valid pairs, and a candle without a pair repeats the last
+// valid pair's value (beta_gap_row below).
 //
 // One wave per symbol walks the row in tiles of 256 candles (4 per lane), with
 // no cross-wave step: waves of different symbols never wait for each other,
@@ -91,6 +94,119 @@ __device__ __forceinline__ int wslot(int t) {
 #define BQ_BW_WAVES 3   // waves per SIMD the MODE 3 register budget is cut for
 #endif
 
+// A row with a candle that lacks a finite return pair (a missing or zero
+// close on either side). The reference drops the pairs with a NaN return and
+// rolls over the compacted rest: the window at t is the last `win` valid
+// pairs however far back they lie, NaN while fewer exist, and NaN while it
+// holds a +-inf return (pandas' rolling takes it for a missing observation
+// without dropping the pair); a candle without a pair of its own repeats the
+// last valid pair's value (the reference's iloc[-1]). The prefix walk lets
+// such a pair add nothing, so it is right wherever the last `win` positions
+// all hold finite pairs and wrong elsewhere. After the walk the same wave
+// passes over the row again, one lane per candle, and recomputes the tiles
+// of 64 candles that hold a candle within `win` of a bad pair: each lane
+// walks back over the row (L2 hits: the walk has just read it) until it
+// holds `win` valid pairs and forms the sums directly about its own pair
+// (x0, y0), with the same-value rule where every x / y / x*y of the window
+// is equal. The benchmark's window stats of the pre-pass (MODE 3) are not
+// read here: they hold the benchmark's own validity, not the pair's.
+template <int MODE>
+__device__ __forceinline__ void beta_pair(const double* __restrict__ rc, const double* __restrict__ rb, int j,
+                                          double& x, double& y) {
+  if (MODE == 1) {
+    x = rc[j];
+    y = rb[j];
+  } else {
+    x = log_return(rc[j], rc[j - 1]);
+    y = MODE >= 2 ? rb[j] : log_return(rb[j], rb[j - 1]);
+  }
+}
+
+__device__ __forceinline__ bool finite_pair(double x, double y) {
+  return fabs(x) <= __DBL_MAX__ && fabs(y) <= __DBL_MAX__;
+}
+
+template <int MODE>
+__device__ __forceinline__ void beta_gap_row(const BetaArgs& A, const double* __restrict__ rc,
+                                             const double* __restrict__ rb, int64_t orow, int win, int lane) {
+  constexpr int t_first = MODE == 1 ? 0 : 1;
+  const int T = A.T;
+  double carb = qnan(), carc = qnan();   // the last valid pair's value before this tile
+  bool car_mem = false;                  // ... is the walk's, at t0 - 1 (the tile before was kept)
+  int dprev = win;                       // candles from t0 - 1 back to the last bad pair, at most win
+  for (int t0 = 0; t0 < T; t0 += WAVE) {
+    const int t = t0 + lane;
+    const bool in = t >= t_first && t < T;
+    double x0 = 0.0, y0 = 0.0;
+    if (in) beta_pair<MODE>(rc, rb, t, x0, y0);
+    const bool have = in && x0 == x0 && y0 == y0;
+    // candles since the last bad pair: below win, the window at t holds it
+    const unsigned long long le = ~0ull >> (WAVE - 1 - lane);
+    const unsigned long long mb = __builtin_amdgcn_ballot_w64(in && !finite_pair(x0, y0)) & le;
+    const int d = mb ? lane - (63 - __builtin_clzll(mb)) : lane + 1 + dprev;
+    dprev = min(__builtin_amdgcn_readlane(d, WAVE - 1), win);
+    if (__builtin_amdgcn_ballot_w64(in && d < win) == 0) {   // the walk's values stand
+      car_mem = true;
+      continue;
+    }
+    if (car_mem) {   // t0 - 1 has a pair and a clean window: its value is the last valid pair's
+      carb = A.beta ? A.beta[orow + t0 - 1] : qnan();
+      carc = A.corr ? A.corr[orow + t0 - 1] : qnan();
+      car_mem = false;
+    }
+    double beta = qnan(), corr = qnan();
+    if (have && finite_pair(x0, y0)) {
+      const double xy0 = x0 * y0;
+      double sx = 0.0, sy = 0.0, sxy = 0.0, su = 0.0, suu = 0.0, sv = 0.0, svv = 0.0;
+      bool samex = true, samey = true, samexy = true;
+      int n = 0;
+      for (int j = t; j >= t_first; --j) {
+        double x, y;
+        beta_pair<MODE>(rc, rb, j, x, y);
+        if (x != x || y != y) continue;    // dropna
+        if (!finite_pair(x, y)) break;     // +-inf in the window: NaN
+        const double xy = x * y, u = x - x0, v = y - y0;
+        sx += x;
+        sy += y;
+        sxy += xy;
+        su += u;
+        sv += v;
+        suu = fma(u, u, suu);
+        svv = fma(v, v, svv);
+        samex = samex && x == x0;
+        samey = samey && y == y0;
+        samexy = samexy && xy == xy0;
+        if (++n == win) break;
+      }
+      if (n == win) {
+        const double mx = samex ? x0 : sx * A.inv_w, my = samey ? y0 : sy * A.inv_w;
+        const double mxy = samexy ? xy0 : sxy * A.inv_w;
+        double vx = samex ? 0.0 : (suu - su * su * A.inv_w) * A.inv_w1;
+        double vy = samey ? 0.0 : (svv - sv * sv * A.inv_w) * A.inv_w1;
+        vx = vx < 0.0 ? 0.0 : vx;
+        vy = vy < 0.0 ? 0.0 : vy;
+        const double cov = (mxy - mx * my) * A.bias;
+        beta = cov * (vy == 0.0 ? qnan() : rcp_nr(vy));
+        corr = cov * rsq_nr(vx * vy);
+      }
+    }
+    // candles without a pair: the nearest lane below that has one, else the carry
+    const unsigned long long below = __builtin_amdgcn_ballot_w64(have) & le;
+    const int src = below ? 63 - __builtin_clzll(below) : 0;
+    const double sb = __shfl(beta, src, WAVE), sc = __shfl(corr, src, WAVE);
+    if (!have) {
+      beta = below ? sb : carb;
+      corr = below ? sc : carc;
+    }
+    carb = readlane_f64(beta, WAVE - 1);
+    carc = readlane_f64(corr, WAVE - 1);
+    if (t < T) {
+      if (A.beta) A.beta[orow + t] = beta;
+      if (A.corr) A.corr[orow + t] = corr;
+    }
+  }
+}
+
 // MODE 0: close / btc prices, returns formed here (first return NaN, first
 // full window at t = w). MODE 2: close prices + the benchmark's returns as one
 // row shared by every symbol (formed once per launch, not once per wave).
@@ -116,8 +232,8 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
   if (T > t_first) {
     rx = PAIRS ? rc[0] : log_return(rc[1], rc[0]);
     ry = PAIRS ? rb[0] : (BRET ? rb[1] : log_return(rb[1], rb[0]));
-    if (rx != rx) rx = 0.0;
-    if (ry != ry) ry = 0.0;
+    if (!(fabs(rx) <= __DBL_MAX__)) rx = 0.0;   // any finite reference serves
+    if (!(fabs(ry) <= __DBL_MAX__)) ry = 0.0;
   }
   // empty prefixes before the row (the halo of the first tile)
 #pragma unroll
@@ -132,6 +248,10 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
   load_lane<BC::K>(rc, BC::K * lane, T, vin, cn);
   load_lane<BC::K>(rb, BC::K * lane, T, vbtc, bn);
   const double wd = (double)win;
+  // nonzero once the lane met a candle inside the row without a finite pair:
+  // the row is recomputed (beta_gap_row). An int, so that it lives in a VGPR:
+  // the walk has scalar registers for nothing more.
+  int gap = 0;
   for (int t0 = 0; t0 < T; t0 += BW_TT) {
     const int tb = t0 + BC::K * lane;
     // MODE 3: the benchmark's window stats of this tile (L2 hits: every symbol
@@ -179,7 +299,7 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
         pbt = b[k];
       }
     }
-    // per-candle terms (a candle without both returns adds nothing), their
+    // per-candle terms (a candle without both returns, finite, adds nothing), their
     // tile-local inclusive prefixes, and the last index where x / y / x*y
     // changed (the same-value rule)
     double q[NS][BC::K];
@@ -196,11 +316,15 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
         pxy = xyprev;
       }
       int lx = -1, ly = -1, lxy = -1;
+      int bad = 0;
 #pragma unroll
       for (int k = 0; k < BC::K; ++k) {
         const int t = tb + k;
-        const bool ok = x[k] == x[k] && y[k] == y[k];
         const double xy = x[k] * y[k];
+        // both returns finite: one test of the product (|log return| < 746: it cannot overflow)
+        const bool ok = __builtin_isfinite(xy);
+        // rows of joined pairs end in NaN padding, which is no gap: there only +-inf
+        if (PAIRS ? __builtin_isinf(x[k]) || __builtin_isinf(y[k]) : !ok && (k > 0 || t != 0)) bad = 1;   // candle 0 has no return
         if (ok) {
           const double u = x[k] - rx;
           acc[0] += x[k];
@@ -223,6 +347,13 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
         px = x[k];
         py = y[k];
         pxy = xy;
+      }
+      if (PAIRS || t0 + BW_TT <= T) {
+        gap |= bad;
+      } else {   // the ragged last tile: the lanes past T hold padding
+#pragma unroll
+        for (int k = 0; k < BC::K; ++k)
+          if (!__builtin_isfinite(x[k] * y[k]) && tb + k >= t_first && tb + k < T) gap = 1;
       }
       xprev = readlane_f64(x[BC::K - 1], WAVE - 1);
       if (!YST) yprev = readlane_f64(y[BC::K - 1], WAVE - 1);
@@ -308,6 +439,10 @@ __global__ __launch_bounds__(WAVE, MODE == 3 ? BQ_BW_WAVES : 2) void beta_wave_k
         for (int s2 = 0; s2 < NS; ++s2) sP[s2][wslot(tb + k)] = q[s2][k] - tot[s2];
     }
   }
+  if (__builtin_amdgcn_ballot_w64(gap != 0) != 0) {   // wave-uniform; never taken on a clean row
+    __threadfence();   // the walk's stores of this row land before the ones that replace them
+    beta_gap_row<MODE>(A, rc, rb, sym * A.ld_out, win, lane);
+  }
 }
 
 // The benchmark's rolling(w) mean and variance (ddof 1) of its log returns
@@ -334,7 +469,7 @@ __global__ __launch_bounds__(BC::NT) void beta_btc_stats_kernel(const double* __
     return y[t];
   };
   double ry = T > 1 ? yv(1) : 0.0;
-  if (ry != ry) ry = 0.0;
+  if (!(fabs(ry) <= __DBL_MAX__)) ry = 0.0;
   if (tid < BC::H) sP[0][BC::slot(tid)] = sP[1][BC::slot(tid)] = 0.0;
   if (tid == 0) sCar = -1;
   for (int t0 = 0; t0 < T; t0 += BC::TT) {
@@ -347,7 +482,7 @@ __global__ __launch_bounds__(BC::NT) void beta_btc_stats_kernel(const double* __
       const int t = tb + k;
       v[k] = yv(t);
       if (bp && t < T) ystat[3 * T + t] = v[k];
-      if (v[k] == v[k]) {
+      if (fabs(v[k]) <= __DBL_MAX__) {   // a missing or +-inf return adds nothing (beta_gap_row)
         const double d = v[k] - ry;
         acc[0] += v[k];
         acc[1] = fma(d, d, acc[1]);

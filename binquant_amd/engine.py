@@ -885,7 +885,15 @@ def beta_corr(
 ) -> dict[str, torch.Tensor]:
     """Rolling beta / correlation of log returns vs the benchmark at every t
     (ContextEvaluator.dynamic_btc_beta_corr, producers/context_evaluator.py:154-194).
-    close: [S, T]; btc_close: [T] index-aligned with the panel."""
+    close: [S, T]; btc_close: [T] index-aligned with the panel.
+
+    Missing (NaN) and zero closes follow the reference's dropna on every
+    prefix [0, t]: the window at t is the last `window` valid return pairs,
+    however far back they lie; NaN while fewer exist, while the benchmark's
+    variance is 0, and while the window holds a +-inf return (a zero close).
+    A candle without a pair of its own (either close missing at t or t - 1)
+    returns the last valid pair's value, so [:, -1] is the reference's
+    iloc[-1] (oracle.indicators_ref.beta_corr_prefix)."""
     close = _check_panel(close, "close")
     S, T = close.shape
     btc = _check_panel(btc_close.reshape(1, -1), "btc_close", (1, T)).contiguous()

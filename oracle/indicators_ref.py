@@ -281,6 +281,37 @@ def beta_corr_series(close, btc_close, window: int = 50) -> tuple[np.ndarray, np
     return beta, corr
 
 
+def beta_corr_prefix(close, btc_close, window: int = 50) -> tuple[np.ndarray, np.ndarray]:
+    """beta_corr_series for closes with missing (NaN) and zero candles: at
+    every candle t the raw beta/corr that ContextEvaluator.dynamic_btc_beta_corr
+    (producers/context_evaluator.py:154-194) takes from the prefix [0, t].
+    The method drops the pairs where either return is NaN and rolls over the
+    compacted pairs, so the window at t is the last `window` valid pairs
+    however far back they lie, and its iloc[-1] at a candle without a pair is
+    the last valid pair's value. Nothing is forward-filled: NaN while fewer
+    than `window` pairs exist, while the variance is 0, and while the window
+    holds a +-inf return (a zero close; pandas' rolling treats it as missing
+    without dropping the pair). Equal to beta_corr_series bit for bit on
+    closes without gaps; pinned to tests/golden/beta_corr_gaps.npz."""
+    c, b = np.asarray(close, float), np.asarray(btc_close, float)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        alt = pd.Series(np.log(c / np.roll(c, 1)))
+        btc = pd.Series(np.log(b / np.roll(b, 1)))
+    alt.iloc[0] = np.nan
+    btc.iloc[0] = np.nan
+    valid = (alt.notna() & btc.notna()).to_numpy()
+    r = pd.concat([alt, btc], axis=1, keys=["alt", "btc"]).dropna()
+    cov = r["alt"].rolling(window).cov(r["btc"])
+    var = r["btc"].rolling(window).var()
+    beta = (cov / var.replace(0, np.nan)).to_numpy()
+    corr = r["alt"].rolling(window).corr(r["btc"]).to_numpy()
+    k = np.cumsum(valid) - 1   # compacted index of the last valid pair up to t
+    at = np.maximum(k, 0)
+    if not len(r):
+        return np.full(len(c), np.nan), np.full(len(c), np.nan)
+    return np.where(k >= 0, beta[at], np.nan), np.where(k >= 0, corr[at], np.nan)
+
+
 def dynamic_btc_beta_corr(close, btc_close, window: int = 50) -> tuple[float, float]:
     """Scalar form at the last row, with the reference's NaN -> 0 mapping and
     the (0, 0) short-history case (rounding is pybinbot's round_numbers: not applied)."""

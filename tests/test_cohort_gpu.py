@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.util import assert_close
+
 pytestmark = pytest.mark.gpu
 
 
@@ -103,7 +105,10 @@ def test_cohort_h1_gap_keeps_newest_bins_and_btc_change(cuda):
     cohort keeps each row's NEWEST bins (bq_resample_tail): h1.bins - 1 is
     the latest hour, h1.dropped counts the oldest bins left out, and the kept
     bins equal the tail of the full read-back resample. Also the a12 BTC
-    change with a missing close at t - 96 (pandas' pad fill)."""
+    change with a missing close at t - 96 (pandas' pad fill), and a11 with
+    those two missing BTC closes and one symbol row that misses a candle of
+    its own inside the last window: btc.beta / btc.corr are the reference's
+    values over the last 50 valid pairs (oracle beta_corr_prefix)."""
     from binquant_amd import engine
     from binquant_amd.cohort import RESAMPLE_AGG, process_cohort
     from oracle import indicators_ref as ref
@@ -118,7 +123,16 @@ def test_cohort_h1_gap_keeps_newest_bins_and_btc_change(cuda):
     btc[-97] = np.nan
     btc[-1] = np.nan
     ins[12] = torch.from_numpy(btc).cuda()
+    c15 = ins[8].cpu().numpy().copy()
+    c15[3, T - 20] = np.nan
+    ins[8] = torch.from_numpy(c15).cuda()
     out = process_cohort(*ins)
+    got_b, got_c = out["btc.beta"].cpu().numpy(), out["btc.corr"].cpu().numpy()
+    for s in range(S):
+        wb, wc = ref.beta_corr_prefix(c15[s], btc, 50)
+        assert_close(got_b[s], wb[-1], f"btc.beta[{s}]", rtol=1e-8, scale=1.0)
+        assert_close(got_c[s], wc[-1], f"btc.corr[{s}]", rtol=1e-8, scale=1.0)
+    assert not np.isnan(got_b[3]) and not np.isnan(got_b[0])
     B1 = T // 4 + 2
     _, res, nb = engine.resample(ins[10], {k: ins[5 + i] for i, k in enumerate(("open", "high", "low", "close", "volume"))},
                                  RESAMPLE_AGG, 3_600_000)

@@ -37,8 +37,10 @@ The cases, S = 3 rows each:
       that window plus one. Rows: a plain walk; a constant run over the tile
       boundary at 2048; a row with a NaN and a +inf.
   beta_corr (bq_beta_corr_ws)   T = 1 / 1023 / 1025 / 2100, windows 50 and 20;
-      the benchmark row holds a NaN and a run of equal closes over the
-      pre-pass's tile boundary at 1024.
+      the benchmark row holds a run of equal closes over the pre-pass's tile
+      boundary at 1024. Every close is finite: rows with missing or zero
+      closes are judged against the reference, not the parent
+      (tests/test_beta_gaps_gpu.py).
 """
 
 from __future__ import annotations
@@ -138,8 +140,6 @@ def beta_inputs(T: int) -> dict[str, np.ndarray]:
     btc = 60000.0 * np.exp(np.cumsum(g.normal(0.0, 0.001, T)))
     r = _run(T, *BETA_RUN)
     btc[r] = btc[r.start]
-    if T > 8:
-        btc[T // 3] = NAN
     return {"close": c, "btc": btc}
 
 
