@@ -65,6 +65,13 @@ Fixtures:
                         market_state_store.py:84): _compute_symbol_features' skip-NaN true
                         range and min_periods=1 windows over such histories
 
+  strategy_gaps.npz     (+ strategy_gaps_fsf.npz; written by make_golden_strategy_gaps.py, not by
+                        this file) rows with missing candles — single NaN closes, candle runs, a
+                        late listing, NaN volume / open / high, a NaN tail, empty resample bins,
+                        gaps at the 1024-candle tile edge, a benchmark with missing candles —
+                        through compute_indicators, compute_pump_score, detect (every column at
+                        every candle) and the a20 helpers on prefix frames around the gaps
+
 Usage: python tests/golden/make_golden.py [--only pins,panel,leadership,inf,btc_change,twins,store_gaps]
 """
 

@@ -8,7 +8,11 @@ panels with halts, gaps, zero volume and NaN candles:
 
 The staged pipelines themselves are pinned to the reference's fixtures
 (tests/test_strategies_gpu.py, tests/test_panel_fixtures_gpu.py), which now run
-the fused passes too."""
+the fused passes too — and on rows with NaN candles as well: the staged side
+of these comparisons, like the fused and the exact one, is held to the real
+reference on gap rows by tests/test_strategy_gaps_gpu.py
+(tests/golden/strategy_gaps.npz), so a NaN rule that both sides here got wrong
+in the same way no longer passes unseen."""
 
 import numpy as np
 import pytest
