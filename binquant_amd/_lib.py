@@ -305,6 +305,24 @@ RF_NFEATURES = 2
 RF_CTX_ROWS = ("regime_is_transitioning", "market_stress_score", "market_regime")
 
 
+class BqBuyTheDipParams(ctypes.Structure):
+    """Mirror of ``bq_buy_the_dip_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("lookback_candles", ctypes.c_int32), ("ema_span", ctypes.c_int32), ("lookback_ms", ctypes.c_int64),
+                ("start_time_ms", ctypes.c_int64), ("min_change_pct", ctypes.c_double),
+                ("max_change_pct", ctypes.c_double)]
+
+
+# bq_buy_the_dip_replay: status codes (BQ_DIP_*, the index is the code: the points where BuyTheDip.signal() returns,
+# in its order; the reference returns silently or with a log line, so the names are this library's) and the value
+# columns' order. market_regime / micro_regime: int8 indices into MARKET_REGIMES / MICRO_REGIMES, negative for None
+(BQ_DIP_EMIT, BQ_DIP_NO_FRAME, BQ_DIP_NOT_READY, BQ_DIP_BEFORE_START, BQ_DIP_NO_REFERENCE, BQ_DIP_OUT_OF_BAND,
+ BQ_DIP_REGIME_BLOCKED, BQ_DIP_NOT_RECLAIMED) = range(8)
+DIP_REASONS = ("emit", "no_frame", "not_enough_data", "before_start_time", "no_reference_price",
+               "change_outside_dip_band", "blocked_trend_regime", "prior_close_and_ema20_not_reclaimed")
+DIP_VALUES = ("reference_price", "change_6h", "ema20")
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -427,6 +445,9 @@ SIGNATURES: dict[str, tuple] = {
     "bq_range_fade_replay": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _PP, _I64, _P, _I64,
                                             _P, _I64, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                             ctypes.POINTER(BqRangeFadeParams), _P, _PP, _I64, _P]),
+    "bq_buy_the_dip_default_params": (None, [ctypes.POINTER(BqBuyTheDipParams)]),
+    "bq_buy_the_dip_replay": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64,
+                                             ctypes.POINTER(BqBuyTheDipParams), _P, _PP, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

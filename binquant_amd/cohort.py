@@ -16,7 +16,8 @@ all S symbols of the cohort in one call:
   strategies' decisions (price_tracker, burst_entry below);
 * 15m frame: indicators_enrichment (:415), the 1h resample (:403-407, a9),
   dynamic_btc_beta_corr (:424, a11: index-aligned frames) and the BTC
-  pct_change(96) (:425-428, a12);
+  pct_change(96) (:425-428, a12), and on request BuyTheDip's decision
+  (buy_the_dip below);
 * the context refresh at the cohort's close: the breadth partials of every
   timestamp and the last timestamp's symbol features
   (live_market_context_accumulator.py:95-297, bq_context_partials);
@@ -75,7 +76,9 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                    sweep_symbol_rank: torch.Tensor | None = None,
                    price_tracker: signals.PriceTrackerState | None = None, ct5: torch.Tensor | None = None,
                    price_tracker_ctx: tuple | None = None, price_tracker_rs: torch.Tensor | None = None,
-                   burst_entry: bool = False, burst_route: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+                   burst_entry: bool = False, burst_route: torch.Tensor | None = None,
+                   buy_the_dip: bool = False, ct15: torch.Tensor | None = None,
+                   dip_regimes: tuple | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -141,9 +144,16 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     burst.qualified_signal): burst.entry_status (uint8) / burst.autotrade
     (bool) [S]. burst_route: allows_long_autotrade per row, bool [S] (or
     [S, T5]; signals.long_autotrade_allows), or None: latest_market_context is
-    None (the message goes out without autotrade). Without these keywords the
-    outputs and launches are unchanged. Returns a flat dict of tensors (names
-    prefixed by the stage)."""
+    None (the message goes out without autotrade). buy_the_dip=True adds, after
+    the 15m frame and on its stream, BuyTheDip.signal()'s decision for the
+    newest 15m candle (signals.buy_the_dip_entry on c15 and ct15, the 15m
+    close_time, int64 [S, T15]; the EMA20 is formed in the pass): dip.status
+    (uint8) / dip.reference_price / dip.change_6h [S]. dip_regimes:
+    (market_regime int8 [1], micro_regime int8 [S]) of
+    signals.buy_the_dip_entry, device tensors the caller updates in place
+    between replays (either may be None), or None: no context. Without these
+    keywords the outputs and launches are unchanged. Returns a flat dict of
+    tensors (names prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -204,6 +214,15 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                                           columns=())
             for k in ("status", "entry", "score", "stop_loss_pct"):
                 out[f"topentry.{k}"] = te[k]
+        if buy_the_dip:   # BuyTheDip.signal() (:127-181 of the strategy) on the cohort's message: the newest candle only
+            if ct15 is None:
+                raise ValueError("process_cohort: buy_the_dip needs ct15")
+            mkt, micro = dip_regimes if dip_regimes is not None else (None, None)
+            newest = torch.full((S,), T15 - 1, dtype=torch.int64, device=c15.device)
+            dip = signals.buy_the_dip_entry(c15, ct15, mkt, micro, from_t=newest,
+                                            columns=("reference_price", "change_6h"))
+            for k in ("status", "reference_price", "change_6h"):
+                out[f"dip.{k}"] = dip[k][:, -1]
 
     def context(out):   # klines_provider.py:181-199
         part, last = engine.context_partials(h15, l15, c15, max_bars=max_bars, last=True)

@@ -1414,8 +1414,8 @@ def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
     return cols, ld
 
 
-# ---- the argument layer of the five replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
-# range_fade): each check raises the text the wrappers raised themselves, with the entry's name substituted
+# ---- the argument layer of the six replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
+# range_fade, buy_the_dip): each check raises the text the wrappers raised themselves, with the entry's name substituted
 
 def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None) -> dict:
     """defaults overlaid with params; int_keys given: every other parameter is a finite float."""
@@ -2172,6 +2172,71 @@ def range_fade_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torc
         _ptr(sy[0]), _ptr(sy[1]), _ptr(sy[2]), _ptr(sy[3]), _ptr(sy[4]), ld_sym, _ptr(lens), _ptr(first_t),
         _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
     _lib.check(st, "bq_range_fade_replay")
+    return status, outs
+
+
+BUY_THE_DIP_DEFAULTS = dict(   # BuyTheDip's class attributes (strategies/coinrule/buy_the_dip.py:34-36) and :67, :159
+    lookback_candles=24, lookback_ms=6 * 3_600_000, start_time_ms=1_776_036_060_000, min_change_pct=-5.0,
+    max_change_pct=-2.0, ema_span=20)
+_DIP_INT_PARAMS = ("lookback_candles", "lookback_ms", "start_time_ms", "ema_span")
+
+
+def _replay_regime(x, name: str, shapes):
+    """x: None (absent) or an int8 code tensor of one of `shapes`."""
+    if x is None:
+        return None
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.int8 or tuple(x.shape) not in shapes:
+        raise ValueError(f"{name}: expected an int8 tensor of shape {' or '.join(str(s) for s in shapes)}")
+    return x
+
+
+@device_entry
+def buy_the_dip_replay(c: torch.Tensor, close_time: torch.Tensor, market_regime: torch.Tensor | None,
+                       micro_regime: torch.Tensor | None, *, ema20: torch.Tensor | None = None, first_t=None,
+                       lens=None, from_t=None, columns=_lib.DIP_VALUES, **params):
+    """BuyTheDip.signal() replayed over the panel
+    (strategies/coinrule/buy_the_dip.py:127-243; bq_buy_the_dip_replay): column
+    t of row s = the method on the message whose frame is
+    df.iloc[first_t[s]:t + 1] with current_price = close[t]; candles
+    max(from_t[s], first_t[s]) .. lens[s] - 1 are replayed. c [S, T] float64
+    with unit stride along T and any row pitch; close_time [S, T] int64 ms,
+    strictly ascending within a row's frame. ema20 [S, T] or None: the frame's
+    close.ewm(span=ema_span, adjust=False, min_periods=1).mean() formed in the
+    pass. market_regime int8 [1] or [T] (_lib.MARKET_REGIMES codes, negative:
+    no context, or None) and micro_regime int8 [S] or [S, T]
+    (_lib.MICRO_REGIMES codes, negative: no features, or None), on the device;
+    None: no context / no features for any candle. Returns (status uint8
+    [S, T] (_lib.BQ_DIP_*), {name: float64 [S, T]} for `columns`, a subset of
+    _lib.DIP_VALUES, NaN where the method did not reach them). params:
+    BUY_THE_DIP_DEFAULTS' keys."""
+    par = _replay_params("buy_the_dip_replay", BUY_THE_DIP_DEFAULTS, params, _DIP_INT_PARAMS)
+    if not float(par["min_change_pct"]) < float(par["max_change_pct"]):
+        raise ValueError("buy_the_dip_replay: min_change_pct must be below max_change_pct")
+    if int(par["lookback_candles"]) < 2 or int(par["lookback_ms"]) <= 0 or int(par["ema_span"]) < 1:
+        raise ValueError("buy_the_dip_replay: lookback_candles >= 2 (the prior close), lookback_ms > 0, ema_span >= 1")
+    columns = tuple(columns)
+    _replay_columns("buy_the_dip_replay", columns, _lib.DIP_VALUES)
+    S, T = _replay_shape(c)
+    _replay_panels([(c, "close")] + ([(ema20, "ema20")] if ema20 is not None else []), S, T)
+    _replay_time(close_time, "close_time", S, T)
+    mk = _replay_regime(market_regime, "market_regime", ((1,), (T,)))
+    mr = _replay_regime(micro_regime, "micro_regime", ((S,), (S, T)))
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    cc = _check_panel(c, "close")
+    em = _check_panel(ema20, "ema20") if ema20 is not None else None
+    ct = _check_ts(close_time, "close_time")
+    _replay_on_device("market_regime / micro_regime", [mk, mr])
+    mk = mk.contiguous() if mk is not None else None
+    mr = mr.contiguous() if mr is not None else None
+    dev = c.device
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqBuyTheDipParams, par, _DIP_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.DIP_VALUES, S, T, dev)
+    st = _lib.load().bq_buy_the_dip_replay(
+        _ptr(cc), _row_stride(cc), _ptr(ct), T, _ptr(em), _row_stride(em) if em is not None else T, _ptr(mk),
+        mk.numel() if mk is not None else 1, _ptr(mr), T if mr is not None and mr.dim() == 2 else 0, _ptr(lens),
+        _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_buy_the_dip_replay")
     return status, outs
 
 

@@ -57,6 +57,13 @@ prefix frame df.iloc[:t + 1]:
                      qualified_signal (strategies/activity_burst_pump.py:160-185),
                      with long_autotrade_allows for allows_long_autotrade
                      (market_regime/regime_routing.py:30-75)
+* buy_the_dip_entry  the decisions of BuyTheDip.signal()
+                     (strategies/coinrule/buy_the_dip.py:127-181) on the 15m
+                     frame: null gate, start time, the 6 h reference candle
+                     found by close_time, the change band, _allows_entry and
+                     the prior-close / EMA20 reclaim, one pass (bq_dip.hip),
+                     with buy_the_dip_routing for the message's autotrade flag
+                     and route (:87-125)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -1105,3 +1112,90 @@ def activity_burst_entry(qualified, route_ok, ctx_ok, *, first_t=None, lens=None
         (CTX & ~F.inp(route_ok), AB_ROUTE_REFUSED), (~F.inp(qualified), AB_NOT_QUALIFIED)], AB_EMIT)
     res = F.run({"status": code, "autotrade": (code == float(AB_EMIT)) & CTX}, S, T)
     return {"status": res["status"].to(torch.uint8), "autotrade": res["autotrade"]}
+
+
+# ---- the 15m dip buyer: BuyTheDip -----------------------------------------------------------------------------------
+# bq_buy_the_dip_replay's status codes: where BuyTheDip.signal() returned, in the method's order (the reference
+# returns silently or with a log line: DIP_REASONS' names are this library's)
+(DIP_EMIT, DIP_NO_FRAME, DIP_NOT_READY, DIP_BEFORE_START, DIP_NO_REFERENCE, DIP_OUT_OF_BAND, DIP_REGIME_BLOCKED,
+ DIP_NOT_RECLAIMED) = range(8)
+DIP_REASONS = dict(enumerate(_lib.DIP_REASONS))
+DIP_VALUES = _lib.DIP_VALUES
+
+
+def buy_the_dip_entry(c, close_time, market_regime, micro_regime, *, ema20=None, first_t=None, lens=None, from_t=None,
+                      columns=DIP_VALUES, **params):
+    """The decisions of BuyTheDip.signal() (strategies/coinrule/buy_the_dip.py
+    :127-181) for every candle of a 15m panel in one pass
+    (engine.buy_the_dip_replay, bq_buy_the_dip_replay). Column t of row s =
+    the method on the message whose frame is df.iloc[first_t[s]:t + 1] with
+    current_price = close[t]; candles from_t[s] .. lens[s] - 1 are replayed.
+    The method keeps no state: a column does not depend on earlier messages.
+    c [S, T] float64, close_time [S, T] int64 ms, strictly ascending within a
+    row's frame: the 6 h reference is the newest candle whose close_time is at
+    least lookback_ms older than the message's, found by time, so a row with
+    a halt gets the candle the method takes and not close[t - 24]. ema20: the
+    method's close.ewm(span=20, adjust=False, min_periods=1).mean() [S, T], or
+    None to form it in the pass (1e-9 of pandas). market_regime int8 [1] or
+    [T] (_lib.MARKET_REGIMES codes; negative: latest_market_context is None,
+    or its market_regime is) and micro_regime int8 [S] or [S, T]
+    (_lib.MICRO_REGIMES codes; negative: the context has no features for the
+    symbol, or their micro_regime is None), both on the device; None: absent
+    for every candle. params: engine.BUY_THE_DIP_DEFAULTS' keys.
+
+    Returns {"status": uint8 [S, T] (DIP_* codes, DIP_REASONS their names; 0 =
+    the message goes out), and the `columns` of DIP_VALUES, float64 [S, T],
+    NaN where the method did not reach them}. _allows_buy_the_dip_autotrade
+    and _resolve_autotrade_route only set the message's autotrade flag and
+    route (buy_the_dip_routing); is_autotrade_suppressed reads the wall clock
+    and stays a host step, as do the message text and the dispatch."""
+    status, vals = engine.buy_the_dip_replay(c, close_time, market_regime, micro_regime, ema20=ema20, first_t=first_t,
+                                             lens=lens, from_t=from_t, columns=columns, **params)
+    return {"status": status, **vals}
+
+
+# BuyTheDip._resolve_autotrade_route's strings (:106-125) as uint8 codes, in the method's order; the two f-string
+# families are expanded over their enums (market_regime_none: the method formats str(None); market_regime_range /
+# market_regime_transitional cannot occur)
+DIP_ROUTE_REASONS = (("market_context_unavailable", "market_transitioning", "market_stress_too_high")
+                     + tuple(f"market_regime_{r.lower()}" for r in _lib.MARKET_REGIMES) + ("market_regime_none",)
+                     + ("symbol_regime_unavailable",)
+                     + tuple(f"symbol_regime_{r.lower()}" for r in _lib.MICRO_REGIMES))
+
+
+def buy_the_dip_routing(context_ok, regime_is_transitioning, market_stress_score, market_regime, features_ok,
+                        micro_regime, max_market_stress: float = 0.35):
+    """BuyTheDip._allows_buy_the_dip_autotrade and _resolve_autotrade_route
+    (strategies/coinrule/buy_the_dip.py:87-125) per (symbol, candle). The
+    context's fields [T] (or [S, T]): context_ok / regime_is_transitioning
+    bool, market_stress_score float64, market_regime int8
+    (_lib.MARKET_REGIMES codes, negative: None); the symbol's features [S, T]:
+    features_ok bool (False: the context has none for the symbol),
+    micro_regime int8 (_lib.MICRO_REGIMES codes, negative: None). Returns
+    (autotrade bool [S, T], reason uint8 [S, T]): the emitted message's flag
+    and DIP_ROUTE_REASONS' index of its route. The two methods disagree on
+    purpose: without features autotrade is True under
+    symbol_regime_unavailable, with features whose micro_regime is None it is
+    False under the same route. Quiet hours (is_autotrade_suppressed) are the
+    host's. One fused element-wise program."""
+    S, T = micro_regime.shape
+    R = DIP_ROUTE_REASONS.index
+    CTX, TRANS, FEAT = F.inp(context_ok), F.inp(regime_is_transitioning), F.inp(features_ok)
+    STRESS = F.inp(market_stress_score)
+    MKT, MR = F.inp(market_regime.to(torch.float64)), F.inp(micro_regime.to(torch.float64))
+    mkt_ok = ((MKT == float(_lib.MARKET_REGIMES.index("RANGE")))
+              | (MKT == float(_lib.MARKET_REGIMES.index("TRANSITIONAL"))))
+    sym_ok = ((MR == float(_lib.MICRO_REGIMES.index("RANGE")))
+              | (MR == float(_lib.MICRO_REGIMES.index("TRANSITIONAL"))))
+    stressed = STRESS >= float(max_market_stress)
+    code = _first_code([
+        (~CTX, R("market_context_unavailable")),
+        (TRANS, R("market_transitioning")),
+        (stressed, R("market_stress_too_high")),
+        (MKT < 0.0, R("market_regime_none")),
+        (~mkt_ok, MKT + float(R("market_regime_" + _lib.MARKET_REGIMES[0].lower()))),
+        (~FEAT | (MR < 0.0), R("symbol_regime_unavailable")),
+    ], MR + float(R("symbol_regime_" + _lib.MICRO_REGIMES[0].lower())))
+    auto = CTX & ~TRANS & ~stressed & mkt_ok & (~FEAT | sym_ok)
+    res = F.run({"reason": code, "autotrade": auto}, S, T)
+    return res["autotrade"], res["reason"].to(torch.uint8)

@@ -64,6 +64,10 @@
  *                         gate, regime_routing, _compute_adx, _compute_zscore,
  *                         _resolve_entry's two band rejections and local_score
  *                         (strategies/range_bb_rsi_mean_reversion.py:66-274)
+ *   bq_buy_the_dip_replay <- BuyTheDip.signal(): the frame and null gate, the 6 h
+ *                         reference candle found by close_time, the change band,
+ *                         _allows_entry and the prior-close / EMA20 reclaim
+ *                         (strategies/coinrule/buy_the_dip.py:49-85, :127-181)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -832,6 +836,81 @@ int bq_range_fade_replay(const double* open, const double* high, const double* l
                          int64_t ld_sym, const int64_t* lens, const int64_t* first_t, const int64_t* from_t,
                          int64_t S, int64_t T, const bq_range_fade_params* params, uint8_t* status,
                          double* const* values, int64_t ld_out, void* stream);
+
+/*
+ * BuyTheDip.signal() replayed over a panel of 15m frames
+ * (strategies/coinrule/buy_the_dip.py:127-243, with _find_reference_price
+ * :49-57, _prior_close_and_ema20 :63-71 and _allows_entry :73-85): column t of
+ * row s is what signal() does on the message whose frame is df.iloc[first:t +
+ * 1], first = first_t[s] (NULL: 0), with current_price = close[t]. The method
+ * keeps no state: a column does not depend on the messages before it. Candles
+ * t = max(from_t[s], first) (from_t NULL: 0) .. lens[s] - 1 (NULL: T) are
+ * replayed.
+ * close [S][ld_px]; close_time [S][ld_ct] int64 ms, strictly ascending within
+ * [first, lens) (the method's normalize_timestamp is exact on integer ms below
+ * 2^53: every time comparison is an integer one). ema20 [S][ld_e] or NULL:
+ * formed in the pass, close.ewm(span=ema_span, adjust=False,
+ * min_periods=1).mean() over the frame, with pandas' update for missing (NaN,
+ * +-inf) closes. market_regime: int8 codes of latest_market_context's
+ * market_regime at the candle's message (TREND_UP, TREND_DOWN, RANGE,
+ * HIGH_STRESS, TRANSITIONAL; negative: no context, or None), regime_T == 1: one
+ * for every candle, regime_T == T: one per candle; NULL: no context.
+ * micro_regime: int8 codes of the symbol's micro_regime in that context
+ * (TREND_UP, TREND_DOWN, RANGE, VOLATILE, TRANSITIONAL; negative: no features,
+ * or None), [S] (ld_m == 0) or [S][ld_m]; NULL: no features. Both are device
+ * memory: a captured graph sees values updated in place.
+ *
+ * Per candle, in the method's order:
+ *   # condition                                          status            lines
+ *   1 t outside [max(from_t, first), lens)               NO_FRAME
+ *   2 t + 1 - first < lookback_candles, or a NaN close   NOT_READY         :137-145
+ *     anywhere in the frame (+-inf is a value): once a
+ *     row holds one at u >= first, every later candle
+ *   3 close_time[t] < start_time_ms                      BEFORE_START      :147-149
+ *   4 no u in [first, t] with close_time[u] <=           NO_REFERENCE      :152-156
+ *     close_time[t] - lookback_ms
+ *   5 change_6h > max_change_pct or                      OUT_OF_BAND       :158-160
+ *     change_6h <= min_change_pct (a NaN goes on)
+ *   6 market_regime or micro_regime is TREND_UP or       REGIME_BLOCKED    :73-85, :170
+ *     TREND_DOWN
+ *   7 not (close[t] > close[t - 1] and                   NOT_RECLAIMED     :59-61, :176
+ *     close[t] > ema20[t])
+ *   0 otherwise                                          EMIT              :183-243
+ * reference_price = close[u] of the LARGEST such u (the method scans the frame
+ * backwards); change_6h = safe_pct(close[t], reference_price) * 100, safe_pct =
+ * (cur - prev) / |prev| and exactly 0.0 where prev == 0 (shared/utils.py:20-23).
+ * The autotrade flag and route, quiet hours, the message text and the dispatch
+ * only shape the emitted message: the caller's.
+ *
+ * status [S][ld_out] bytes (BQ_DIP_*), values: NULL or BQ_DIP_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_DIP_V_* order,
+ * NaN where the method did not reach them (reference_price / change_6h: status
+ * 1-4; ema20: every status but 0 and 7). params NULL:
+ * bq_buy_the_dip_default_params. BQ_EINVAL, before any launch, unless every
+ * ld >= T (ld_m: or 0), regime_T is 1 or T, the limits are finite with
+ * min_change_pct < max_change_pct, lookback_candles >= 2, lookback_ms > 0 and
+ * ema_span >= 1. S == 0 or T == 0: BQ_OK.
+ */
+#define BQ_DIP_NVALUES 3
+#define BQ_DIP_REGIME_TREND_UP 0     /* market_regime / micro_regime "TREND_UP" */
+#define BQ_DIP_REGIME_TREND_DOWN 1   /* and "TREND_DOWN" */
+typedef struct bq_buy_the_dip_params {
+  int32_t lookback_candles;   /* 24 LOOKBACK_CANDLES */
+  int32_t ema_span;           /* 20 (:67) */
+  int64_t lookback_ms;        /* LOOKBACK_HOURS 6 x 3600000 */
+  int64_t start_time_ms;      /* START_TIME 2026-04-12 23:21 UTC = 1776036060000 */
+  double min_change_pct;      /* -5 (:159) */
+  double max_change_pct;      /* -2 (:159) */
+} bq_buy_the_dip_params;
+enum { BQ_DIP_EMIT = 0, BQ_DIP_NO_FRAME, BQ_DIP_NOT_READY, BQ_DIP_BEFORE_START, BQ_DIP_NO_REFERENCE,
+       BQ_DIP_OUT_OF_BAND, BQ_DIP_REGIME_BLOCKED, BQ_DIP_NOT_RECLAIMED };
+enum { BQ_DIP_V_REFERENCE = 0, BQ_DIP_V_CHANGE, BQ_DIP_V_EMA };
+void bq_buy_the_dip_default_params(bq_buy_the_dip_params* p);
+int bq_buy_the_dip_replay(const double* close, int64_t ld_px, const int64_t* close_time, int64_t ld_ct,
+                          const double* ema20, int64_t ld_e, const int8_t* market_regime, int64_t regime_T,
+                          const int8_t* micro_regime, int64_t ld_m, const int64_t* lens, const int64_t* first_t,
+                          const int64_t* from_t, int64_t S, int64_t T, const bq_buy_the_dip_params* params,
+                          uint8_t* status, double* const* values, int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t
