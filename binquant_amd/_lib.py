@@ -323,6 +323,25 @@ DIP_REASONS = ("emit", "no_frame", "not_enough_data", "before_start_time", "no_r
 DIP_VALUES = ("reference_price", "change_6h", "ema20")
 
 
+class BqBbExtremeParams(ctypes.Structure):
+    """Mirror of ``bq_bb_extreme_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("lookback", ctypes.c_int32), ("rsi_window", ctypes.c_int32), ("oversold_rsi", ctypes.c_double),
+                ("overbought_rsi", ctypes.c_double), ("max_lower_band_position", ctypes.c_double),
+                ("min_upper_band_position", ctypes.c_double)]
+
+
+# bq_bb_extreme_replay: status codes (BQ_BBX_*, the index is the code: the points where BBExtremeReversion.signal()
+# returns, in its order; the names restate its log lines and evaluate()'s reasons) and the value columns' order.
+# direction: bq_direction as a double (0.0 LONG = buy, 1.0 SHORT = sell)
+(BQ_BBX_EMIT, BQ_BBX_NO_FRAME, BQ_BBX_NOT_ENOUGH_DATA, BQ_BBX_NULLS, BQ_BBX_NO_RSI, BQ_BBX_INVALID_BAND,
+ BQ_BBX_NO_EXTREME) = range(7)
+BBX_REASONS = ("emit", "no_frame", "not_enough_data", "recent_data_contains_nulls", "not_enough_candles_for_rsi",
+               "invalid_band_spread", "no_extreme")
+BBX_VALUES = ("rsi_value", "band_position", "bb_width", "distance_from_mid_pct", "direction")
+BBX_MAX_LOOKBACK = 64
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -448,6 +467,9 @@ SIGNATURES: dict[str, tuple] = {
     "bq_buy_the_dip_default_params": (None, [ctypes.POINTER(BqBuyTheDipParams)]),
     "bq_buy_the_dip_replay": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64,
                                              ctypes.POINTER(BqBuyTheDipParams), _P, _PP, _I64, _P]),
+    "bq_bb_extreme_default_params": (None, [ctypes.POINTER(BqBbExtremeParams)]),
+    "bq_bb_extreme_replay": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                            ctypes.POINTER(BqBbExtremeParams), _P, _PP, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

@@ -1414,8 +1414,8 @@ def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
     return cols, ld
 
 
-# ---- the argument layer of the six replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
-# range_fade, buy_the_dip): each check raises the text the wrappers raised themselves, with the entry's name substituted
+# ---- the argument layer of the seven replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
+# range_fade, buy_the_dip, bb_extreme): each check raises the text the wrappers raised themselves, with the entry's name substituted
 
 def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None) -> dict:
     """defaults overlaid with params; int_keys given: every other parameter is a finite float."""
@@ -2237,6 +2237,54 @@ def buy_the_dip_replay(c: torch.Tensor, close_time: torch.Tensor, market_regime:
         mk.numel() if mk is not None else 1, _ptr(mr), T if mr is not None and mr.dim() == 2 else 0, _ptr(lens),
         _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
     _lib.check(st, "bq_buy_the_dip_replay")
+    return status, outs
+
+
+BB_EXTREME_DEFAULTS = dict(   # BBExtremeReversion's class attributes (strategies/coinrule/bb_extreme_reversion.py:50-67)
+    lookback=30, rsi_window=2, oversold_rsi=5.0, overbought_rsi=95.0, max_lower_band_position=0.0,
+    min_upper_band_position=1.0)
+_BBX_INT_PARAMS = ("lookback", "rsi_window")
+
+
+@device_entry
+def bb_extreme_replay(c: torch.Tensor, bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tensor, *,
+                      first_t=None, lens=None, from_t=None, columns=_lib.BBX_VALUES, **params):
+    """BBExtremeReversion.signal() replayed over the panel, as it runs with
+    ENABLED true (strategies/coinrule/bb_extreme_reversion.py:234-285;
+    bq_bb_extreme_replay): column t of row s = the method on the message whose
+    frame is df.iloc[first_t[s]:t + 1] with current_price = close[t] and the
+    bands of candle t; candles max(from_t[s], first_t[s]) .. lens[s] - 1 are
+    replayed. c / bb_upper / bb_mid / bb_lower [S, T] float64 with unit stride
+    along T and any row pitch. The bands are taken as given: the evaluator's
+    round_numbers(.., 6) on bb_spreads is the caller's step. The RSI is
+    _compute_rsi's, pandas' rolling mean replayed over each candle's own last
+    `lookback` closes, bit for bit. Returns (status uint8 [S, T]
+    (_lib.BQ_BBX_*), {name: float64 [S, T]} for `columns`, a subset of
+    _lib.BBX_VALUES, NaN where the method did not reach evaluate). params:
+    BB_EXTREME_DEFAULTS' keys; rsi_window + 1 > lookback is the method's own
+    "not enough candles" branch, not an error."""
+    par = _replay_params("bb_extreme_replay", BB_EXTREME_DEFAULTS, params, _BBX_INT_PARAMS)
+    if not 1 <= int(par["lookback"]) <= _lib.BBX_MAX_LOOKBACK:
+        raise ValueError(f"bb_extreme_replay: lookback in 1..{_lib.BBX_MAX_LOOKBACK}")
+    if int(par["rsi_window"]) < 1:
+        raise ValueError("bb_extreme_replay: rsi_window must be >= 1")
+    columns = tuple(columns)
+    _replay_columns("bb_extreme_replay", columns, _lib.BBX_VALUES)
+    S, T = _replay_shape(c)
+    bb = [(bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower")]
+    _replay_panels([(c, "close")] + bb, S, T)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    cc = _check_panel(c, "close")
+    bbs, ld_bb = _common_pitch([_check_panel(x, n) for x, n in bb])
+    _replay_on_device("close / bb_upper / bb_mid / bb_lower", [cc, *bbs])
+    dev = c.device
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqBbExtremeParams, par, _BBX_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.BBX_VALUES, S, T, dev)
+    st = _lib.load().bq_bb_extreme_replay(
+        _ptr(cc), _row_stride(cc), _ptr(bbs[0]), _ptr(bbs[1]), _ptr(bbs[2]), ld_bb, _ptr(lens), _ptr(first_t),
+        _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_bb_extreme_replay")
     return status, outs
 
 

@@ -1199,3 +1199,115 @@ def buy_the_dip_routing(context_ok, regime_is_transitioning, market_stress_score
     auto = CTX & ~TRANS & ~stressed & mkt_ok & (~FEAT | sym_ok)
     res = F.run({"reason": code, "autotrade": auto}, S, T)
     return res["autotrade"], res["reason"].to(torch.uint8)
+
+
+# ---- the RSI(2) fade at the Bollinger extremes: BBExtremeReversion --------------------------------------------------
+# bq_bb_extreme_replay's status codes: where BBExtremeReversion.signal() returned, in the method's order (the names
+# restate its log lines and evaluate()'s reasons)
+(BBX_EMIT, BBX_NO_FRAME, BBX_NOT_ENOUGH_DATA, BBX_NULLS, BBX_NO_RSI, BBX_INVALID_BAND, BBX_NO_EXTREME) = range(7)
+BBX_REASONS = dict(enumerate(_lib.BBX_REASONS))
+BBX_VALUES = _lib.BBX_VALUES
+BBX_BUY, BBX_SELL = 0.0, 1.0   # the direction column: bq_direction LONG / SHORT
+
+
+def bb_extreme_entry(c, bb_upper, bb_mid, bb_lower, *, first_t=None, lens=None, from_t=None, columns=BBX_VALUES,
+                     **params):
+    """The decisions of BBExtremeReversion.signal() (strategies/coinrule/
+    bb_extreme_reversion.py:234-285 with evaluate :152-232 and _compute_rsi
+    :134-150) for every candle of a 15m panel in one pass
+    (engine.bb_extreme_replay, bq_bb_extreme_replay). Column t of row s = the
+    method on the message whose frame is df.iloc[first_t[s]:t + 1] with
+    current_price = close[t] and bb_high / bb_mid / bb_low = the bands of
+    candle t; candles from_t[s] .. lens[s] - 1 are replayed. The method keeps
+    no state: a column does not depend on earlier messages. ENABLED is not
+    replayed: the panel form answers what the method does when enabled.
+    c / bb_upper / bb_mid / bb_lower [S, T] float64. The bands are taken as
+    given: the evaluator's round_numbers(.., 6) on bb_spreads is the caller's
+    step, applied before the call. The RSI is local to each frame:
+    rolling(rsi_window).mean() over the gains and losses of df.tail(lookback)
+    is an online sum started at that frame's first row, so its last value
+    depends on all `lookback` closes; the pass replays that sum for every
+    candle, bit for bit with pandas 2.3.3 (a row-wide rolling mean is a
+    different number after a spike). params: engine.BB_EXTREME_DEFAULTS'
+    keys.
+
+    Returns {"status": uint8 [S, T] (BBX_* codes, BBX_REASONS their names; 0 =
+    the message goes out), and the `columns` of BBX_VALUES, float64 [S, T],
+    NaN where the method did not reach evaluate}: rsi_value (50.0 under
+    BBX_NO_RSI), band_position, bb_width, distance_from_mid_pct, and direction
+    (BBX_BUY / BBX_SELL) on emitted messages alone. supports_autotrade and
+    _resolve_directional_autotrade only set the message's autotrade flag and
+    route (bb_extreme_routing); the message text, the dispatch and
+    process_autotrade_restrictions stay host steps."""
+    status, vals = engine.bb_extreme_replay(c, bb_upper, bb_mid, bb_lower, first_t=first_t, lens=lens, from_t=from_t,
+                                            columns=columns, **params)
+    return {"status": status, **vals}
+
+
+# supports_autotrade's and _resolve_directional_autotrade's strings (:86-132) as uint8 codes, in the methods' order;
+# the f-string families are expanded over their enums (market_regime_none: the method formats str(None);
+# market_regime_range cannot occur; only RANGE reaches market_{slug}_unstable_allowed / _stable) and over
+# MICRO_REGIME_BLOCKING_TRANSITIONS
+BBX_BLOCKING_TRANSITIONS = ("VOLATILITY_EXPANSION", "BREAKDOWN", "ENTERED_TRANSITIONAL")
+BBX_ROUTE_REASONS = (("market_context_unavailable", "market_transitioning", "market_stress_too_high")
+                     + tuple(f"market_regime_{r.lower()}" for r in _lib.MARKET_REGIMES) + ("market_regime_none",)
+                     + ("market_range_unstable_allowed", "market_range_stable", "symbol_features_unavailable")
+                     + tuple(f"symbol_transition_{r.lower()}" for r in BBX_BLOCKING_TRANSITIONS)
+                     + ("symbol_micro_regime_unstable", "symbol_regime_not_shortable",
+                        "symbol_regime_trend_down_for_long"))
+
+
+def bb_extreme_routing(context_ok, regime_is_transitioning, timestamp, regime_stable_since, market_stress_score,
+                       market_regime, features_ok, micro_regime, micro_transition, micro_regime_strength, direction,
+                       stress_threshold: float = 0.35, min_age_ms: int = 30 * 60 * 1000, min_strength: float = 0.5):
+    """BBExtremeReversion.supports_autotrade and
+    _resolve_directional_autotrade (strategies/coinrule/
+    bb_extreme_reversion.py:86-132, with is_regime_stable,
+    market_regime/regime_routing.py:22-44) per (symbol, candle). The context's
+    fields [T] (or [S, T]): context_ok / regime_is_transitioning bool,
+    timestamp / regime_stable_since int64 ms (regime_stable_since negative:
+    None), market_stress_score float64, market_regime int8
+    (_lib.MARKET_REGIMES codes, negative: None); the symbol's features [S, T]:
+    features_ok bool (False: the context has none for the symbol),
+    micro_regime / micro_transition int8 (_lib.MICRO_REGIMES /
+    MICRO_TRANSITIONS codes, negative: None), micro_regime_strength float64;
+    direction float64 [S, T]: bb_extreme_entry's column (BBX_BUY / BBX_SELL;
+    NaN, no message: neither directional test applies). The regime's age
+    max(timestamp - regime_stable_since, 0) is formed in int64 before it
+    enters the program, as long_autotrade_allows forms it. Returns (autotrade
+    bool [S, T], route uint8 [S, T]): the emitted message's flag and
+    BBX_ROUTE_REASONS' index of its route; an allowed message keeps the market
+    route (market_range_unstable_allowed or market_range_stable). As in the
+    methods: a NaN micro_regime_strength passes the < min_strength test; a
+    None micro regime is not shortable for a sell and allowed for a buy. One
+    fused element-wise program."""
+    S, T = micro_regime.shape
+    R = BBX_ROUTE_REASONS.index
+    age = (timestamp - regime_stable_since).clamp_min(0)
+    AGE = F.inp(torch.where(regime_stable_since < 0, torch.full_like(age, -1), age).to(torch.float64))
+    CTX, TRANS, FEAT = F.inp(context_ok), F.inp(regime_is_transitioning), F.inp(features_ok)
+    STRESS, STRENGTH, DIR = F.inp(market_stress_score), F.inp(micro_regime_strength), F.inp(direction)
+    MKT = F.inp(market_regime.to(torch.float64))
+    MR, MT = F.inp(micro_regime.to(torch.float64)), F.inp(micro_transition.to(torch.float64))
+    mi, tr = _lib.MICRO_REGIMES.index, _lib.MICRO_TRANSITIONS.index
+    shortable = ((MR == float(mi("RANGE"))) | (MR == float(mi("TRANSITIONAL"))) | (MR == float(mi("TREND_DOWN"))))
+    base = F.where((AGE < 0.0) | (AGE < float(min_age_ms)), float(R("market_range_unstable_allowed")),
+                   float(R("market_range_stable")))
+    refusals = [
+        (~CTX, R("market_context_unavailable")),
+        (TRANS, R("market_transitioning")),
+        (STRESS >= float(stress_threshold), R("market_stress_too_high")),
+        (MKT < 0.0, R("market_regime_none")),
+        (MKT != float(_lib.MARKET_REGIMES.index("RANGE")),
+         MKT + float(R("market_regime_" + _lib.MARKET_REGIMES[0].lower()))),
+        (~FEAT, R("symbol_features_unavailable")),
+    ] + [(MT == float(tr(name)), R("symbol_transition_" + name.lower())) for name in BBX_BLOCKING_TRANSITIONS] + [
+        (STRENGTH < float(min_strength), R("symbol_micro_regime_unstable")),
+        ((DIR == BBX_SELL) & ~shortable, R("symbol_regime_not_shortable")),
+        ((DIR == BBX_BUY) & (MR == float(mi("TREND_DOWN"))), R("symbol_regime_trend_down_for_long")),
+    ]
+    refused = refusals[0][0]
+    for cond, _ in refusals[1:]:
+        refused = refused | cond
+    res = F.run({"route": _first_code(refusals, base), "autotrade": ~refused}, S, T)
+    return res["autotrade"], res["route"].to(torch.uint8)

@@ -68,6 +68,10 @@
  *                         reference candle found by close_time, the change band,
  *                         _allows_entry and the prior-close / EMA20 reclaim
  *                         (strategies/coinrule/buy_the_dip.py:49-85, :127-181)
+ *   bq_bb_extreme_replay <- BBExtremeReversion.signal(): the frame and null gate,
+ *                         _compute_rsi with pandas' roll_mean over the frame's last
+ *                         30 closes, evaluate's band position and the two extremes
+ *                         (strategies/coinrule/bb_extreme_reversion.py:134-285)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -911,6 +915,82 @@ int bq_buy_the_dip_replay(const double* close, int64_t ld_px, const int64_t* clo
                           const int8_t* micro_regime, int64_t ld_m, const int64_t* lens, const int64_t* first_t,
                           const int64_t* from_t, int64_t S, int64_t T, const bq_buy_the_dip_params* params,
                           uint8_t* status, double* const* values, int64_t ld_out, void* stream);
+
+/*
+ * BBExtremeReversion.signal() replayed over a panel of 15m frames
+ * (strategies/coinrule/bb_extreme_reversion.py:234-285, with evaluate :152-232
+ * and _compute_rsi :134-150): column t of row s is what signal() does, were
+ * ENABLED true, on the message whose frame is df.iloc[first:t + 1], first =
+ * first_t[s] (NULL: 0), with current_price = close[t] and bb_high / bb_mid /
+ * bb_low = the bands of candle t. The method keeps no state: a column does not
+ * depend on the messages before it. Candles t = max(from_t[s], first) (from_t
+ * NULL: 0) .. lens[s] - 1 (NULL: T) are replayed.
+ * close [S][ld_px]; bb_upper / bb_mid / bb_lower [S][ld_bb], taken as given: the
+ * evaluator's round_numbers(.., 6) on bb_spreads is the caller's step.
+ *
+ * Per candle, in the method's order:
+ *   # condition                                          status            lines
+ *   1 t outside [max(from_t, first), lens)               NO_FRAME
+ *   2 t + 1 - first < lookback                           NOT_ENOUGH_DATA   :255
+ *   3 a NaN among close[t - lookback + 1 .. t]           NULLS             :264
+ *     (+-inf is a value)
+ *   4 _compute_rsi returned None: rsi_window + 1 >       NO_RSI            :138, :146
+ *     lookback, or the last RSI is NaN (a +-inf
+ *     difference in the last window, or both means 0)
+ *   5 band_span = bb_upper - bb_lower <= 0 (a NaN span   INVALID_BAND      :187
+ *     goes on, with band_position 0.5)
+ *   6 neither rsi_value <= oversold_rsi and              NO_EXTREME        :194-232
+ *     band_position <= max_lower_band_position (buy)
+ *     nor rsi_value >= overbought_rsi and band_position
+ *     >= min_upper_band_position (sell); buy is tested
+ *     first
+ *   0 otherwise                                          EMIT
+ * The RSI is the frame's own: with g = delta.where(delta > 0, 0.0), q =
+ * -delta.where(delta < 0, 0.0) over the differences of df.tail(lookback)'s
+ * close (the first is NaN: g 0.0, q -0.0), gain and loss are
+ * .rolling(rsi_window).mean() as pandas 2.3.3's roll_mean forms it, replayed
+ * from the frame's first row for every candle: an online sum to which a row is
+ * added (y = v - ca; t = sum + y; ca = t - sum - y; sum = t) and from which row
+ * j - rsi_window is removed first (the same with -v and a compensation of its
+ * own); a +-inf row is a missing observation (fewer than rsi_window
+ * observations: NaN); the mean is sum / nobs, but the newest value itself where
+ * the last nobs rows were all equal, and 0 where no row of the window has the
+ * sign bit and the quotient is negative, or every row has it and the quotient
+ * is positive. rsi = 100 - 100 / (1 + gain / loss) in IEEE arithmetic (a loss of
+ * -0.0 gives 100, 0 / -0.0 gives None), then max(0.0, min(100.0, rsi)).
+ * band_position = (close - bb_lower) / band_span where band_span > 0, else 0.5;
+ * bb_width = band_span / bb_mid and distance_from_mid_pct = (close - bb_mid) /
+ * bb_mid * 100 where bb_mid > 0, else 0.0 (a NaN bb_mid: 0.0). ENABLED, the
+ * autotrade flag and route, the message text and the dispatch are the caller's.
+ *
+ * status [S][ld_out] bytes (BQ_BBX_*), values: NULL or BQ_BBX_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_BBX_V_* order,
+ * NaN where the method did not reach evaluate (status 1-3): rsi_value (50.0 on
+ * NO_RSI), band_position, bb_width, distance_from_mid_pct, and direction
+ * (bq_direction: 0.0 LONG for a buy, 1.0 SHORT for a sell) on EMIT alone.
+ * params NULL: bq_bb_extreme_default_params. BQ_EINVAL, before any launch, unless
+ * every ld >= T, the four thresholds are finite, 1 <= lookback <=
+ * BQ_BBX_MAX_LOOKBACK (a candle's frame reaches at most one 64-candle step back)
+ * and rsi_window >= 1. S == 0 or T == 0: BQ_OK.
+ */
+#define BQ_BBX_MAX_LOOKBACK 64
+#define BQ_BBX_NVALUES 5
+typedef struct bq_bb_extreme_params {
+  int32_t lookback;                 /* 30  LOOKBACK_CANDLES */
+  int32_t rsi_window;               /* 2   DEFAULT_RSI_WINDOW */
+  double oversold_rsi;              /* 5   DEFAULT_OVERSOLD_RSI */
+  double overbought_rsi;            /* 95  DEFAULT_OVERBOUGHT_RSI */
+  double max_lower_band_position;   /* 0   DEFAULT_MAX_LOWER_BAND_POSITION */
+  double min_upper_band_position;   /* 1   DEFAULT_MIN_UPPER_BAND_POSITION */
+} bq_bb_extreme_params;
+enum { BQ_BBX_EMIT = 0, BQ_BBX_NO_FRAME, BQ_BBX_NOT_ENOUGH_DATA, BQ_BBX_NULLS, BQ_BBX_NO_RSI, BQ_BBX_INVALID_BAND,
+       BQ_BBX_NO_EXTREME };
+enum { BQ_BBX_V_RSI = 0, BQ_BBX_V_POSITION, BQ_BBX_V_WIDTH, BQ_BBX_V_DISTANCE, BQ_BBX_V_DIRECTION };
+void bq_bb_extreme_default_params(bq_bb_extreme_params* p);
+int bq_bb_extreme_replay(const double* close, int64_t ld_px, const double* bb_upper, const double* bb_mid,
+                         const double* bb_lower, int64_t ld_bb, const int64_t* lens, const int64_t* first_t,
+                         const int64_t* from_t, int64_t S, int64_t T, const bq_bb_extreme_params* params,
+                         uint8_t* status, double* const* values, int64_t ld_out, void* stream);
 
 /*
  * RelativeStrengthImpulseRider._features at every prefix t
