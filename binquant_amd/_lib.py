@@ -342,6 +342,26 @@ BBX_VALUES = ("rsi_value", "band_position", "bb_width", "distance_from_mid_pct",
 BBX_MAX_LOOKBACK = 64
 
 
+class BqRsReversalParams(ctypes.Structure):
+    """Mirror of ``bq_rs_reversal_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("window", ctypes.c_int32), ("reserved", ctypes.c_int32), ("quantile", ctypes.c_double),
+                ("avg_return_max", ctypes.c_double), ("rs_min", ctypes.c_double)]
+
+
+# bq_rs_reversal_replay: status codes (BQ_RSR_*, the index is the code: the points where
+# RelativeStrengthReversalRange.signal() returns, in its order; 3, 4, 6, 7, 8 are regime_routing's own reasons, 5 its
+# "market_regime_<name>" by the fixed part; the others are this library's names) and the value columns' order.
+# market_regime: int8 indices into MARKET_REGIMES, negative for None
+(BQ_RSR_EMIT, BQ_RSR_NO_FRAME, BQ_RSR_SHORT_FRAME, BQ_RSR_NO_CONTEXT, BQ_RSR_REGIME_NONE, BQ_RSR_NOT_RANGE,
+ BQ_RSR_MARKET_NOT_WEAK, BQ_RSR_NO_FEATURES, BQ_RSR_RS_INSUFFICIENT, BQ_RSR_DEAD_TAPE) = range(10)
+RSR_REASONS = ("emit", "no_frame", "short_frame", "market_context_unavailable",
+               "market_regime_unavailable", "market_regime_not_range", "market_avg_return_not_weak_enough",
+               "symbol_regime_unavailable", "symbol_rs_vs_btc_insufficient", "dead_tape")
+RSR_VALUES = ("volume_floor",)
+RSR_MAX_WINDOW = 192
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -470,6 +490,9 @@ SIGNATURES: dict[str, tuple] = {
     "bq_bb_extreme_default_params": (None, [ctypes.POINTER(BqBbExtremeParams)]),
     "bq_bb_extreme_replay": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                             ctypes.POINTER(BqBbExtremeParams), _P, _PP, _I64, _P]),
+    "bq_rs_reversal_default_params": (None, [ctypes.POINTER(BqRsReversalParams)]),
+    "bq_rs_reversal_replay": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                             ctypes.POINTER(BqRsReversalParams), _P, _PP, _I64, _P]),
     "bq_beta_corr": (ctypes.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64, _P]),
     "bq_rolling": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _I64, _P]),
     "bq_rolling_quantile_cross": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _I32, _I32, ctypes.c_double, _P, _I64,

@@ -16,8 +16,8 @@ all S symbols of the cohort in one call:
   strategies' decisions (price_tracker, burst_entry below);
 * 15m frame: indicators_enrichment (:415), the 1h resample (:403-407, a9),
   dynamic_btc_beta_corr (:424, a11: index-aligned frames) and the BTC
-  pct_change(96) (:425-428, a12), and on request BuyTheDip's decision
-  (buy_the_dip below);
+  pct_change(96) (:425-428, a12), and on request BuyTheDip's and
+  RelativeStrengthReversalRange's decisions (buy_the_dip, rs_reversal below);
 * the context refresh at the cohort's close: the breadth partials of every
   timestamp and the last timestamp's symbol features
   (live_market_context_accumulator.py:95-297, bq_context_partials);
@@ -78,7 +78,7 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                    price_tracker_ctx: tuple | None = None, price_tracker_rs: torch.Tensor | None = None,
                    burst_entry: bool = False, burst_route: torch.Tensor | None = None,
                    buy_the_dip: bool = False, ct15: torch.Tensor | None = None,
-                   dip_regimes: tuple | None = None) -> dict[str, torch.Tensor]:
+                   dip_regimes: tuple | None = None, rs_reversal: tuple | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -151,9 +151,14 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     (uint8) / dip.reference_price / dip.change_6h [S]. dip_regimes:
     (market_regime int8 [1], micro_regime int8 [S]) of
     signals.buy_the_dip_entry, device tensors the caller updates in place
-    between replays (either may be None), or None: no context. Without these
-    keywords the outputs and launches are unchanged. Returns a flat dict of
-    tensors (names prefixed by the stage)."""
+    between replays (either may be None), or None: no context. rs_reversal:
+    (context_ok, market_regime, average_return, features_ok, rs) of
+    signals.rs_reversal_entry, device tensors the caller updates in place
+    between replays (context_ok / features_ok may be None): adds, after the
+    15m frame and on its stream, RelativeStrengthReversalRange.signal()'s
+    decision for the newest 15m candle on v15: rsr.status (uint8) /
+    rsr.volume_floor [S]. Without these keywords the outputs and launches are
+    unchanged. Returns a flat dict of tensors (names prefixed by the stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -223,6 +228,11 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                                             columns=("reference_price", "change_6h"))
             for k in ("status", "reference_price", "change_6h"):
                 out[f"dip.{k}"] = dip[k][:, -1]
+        if rs_reversal is not None:   # RelativeStrengthReversalRange.signal() (:75-101) on the newest candle only
+            cok, mkt, avg, fok, rs = rs_reversal
+            newest = torch.full((S,), T15 - 1, dtype=torch.int64, device=c15.device)
+            rsr = signals.rs_reversal_entry(v15, cok, mkt, avg, fok, rs, from_t=newest)
+            out["rsr.status"], out["rsr.volume_floor"] = rsr["status"][:, -1], rsr["volume_floor"][:, -1]
 
     def context(out):   # klines_provider.py:181-199
         part, last = engine.context_partials(h15, l15, c15, max_bars=max_bars, last=True)

@@ -1414,8 +1414,8 @@ def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
     return cols, ld
 
 
-# ---- the argument layer of the seven replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
-# range_fade, buy_the_dip, bb_extreme): each check raises the text the wrappers raised themselves, with the entry's name substituted
+# ---- the argument layer of the eight replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
+# range_fade, buy_the_dip, bb_extreme, rs_reversal): each check raises the text the wrappers raised themselves, with the entry's name substituted
 
 def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None) -> dict:
     """defaults overlaid with params; int_keys given: every other parameter is a finite float."""
@@ -2285,6 +2285,76 @@ def bb_extreme_replay(c: torch.Tensor, bb_upper: torch.Tensor, bb_mid: torch.Ten
         _ptr(cc), _row_stride(cc), _ptr(bbs[0]), _ptr(bbs[1]), _ptr(bbs[2]), ld_bb, _ptr(lens), _ptr(first_t),
         _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
     _lib.check(st, "bq_bb_extreme_replay")
+    return status, outs
+
+
+RS_REVERSAL_DEFAULTS = dict(   # RelativeStrengthReversalRange's class attributes
+    window=96, quantile=0.20, avg_return_max=-0.02, rs_min=0.05)   # (strategies/relative_strength_reversal_range.py:38-41)
+_RSR_INT_PARAMS = ("window",)
+
+
+@device_entry
+def rs_reversal_replay(volume: torch.Tensor, context_ok: torch.Tensor | None, market_regime: torch.Tensor,
+                       average_return: torch.Tensor, features_ok: torch.Tensor | None, rs: torch.Tensor, *,
+                       first_t=None, lens=None, from_t=None, columns=_lib.RSR_VALUES, **params):
+    """RelativeStrengthReversalRange.signal() replayed over the panel
+    (strategies/relative_strength_reversal_range.py:56-101;
+    bq_rs_reversal_replay): column t of row s = the method on the message
+    whose frame is df.iloc[first_t[s]:t + 1]; candles max(from_t[s],
+    first_t[s]) .. lens[s] - 1 are replayed. volume [S, T] float64 with unit
+    stride along T and any row pitch. The context of candle t's message, on the
+    device, [1] (one context for every candle) or [T]: context_ok bool / uint8
+    (None: present), market_regime int8 (_lib.MARKET_REGIMES codes, negative:
+    None), average_return float64. The symbol's entry in the context's
+    snapshot, [S] or [S, T]: features_ok bool / uint8 (None: present) and rs
+    float64, its relative_strength_vs_btc. The volume floor is Series.quantile
+    over the frame's last `window` volumes (numpy's two-sided lerp over the
+    non-NaN rows, +-inf a value), formed only in the 64-candle steps where a
+    candle passes the route. Returns (status uint8 [S, T] (_lib.BQ_RSR_*),
+    {name: float64 [S, T]} for `columns`, a subset of _lib.RSR_VALUES, NaN
+    where the method did not reach the floor). params: RS_REVERSAL_DEFAULTS'
+    keys."""
+    par = _replay_params("rs_reversal_replay", RS_REVERSAL_DEFAULTS, params, _RSR_INT_PARAMS)
+    if not 1 <= int(par["window"]) <= _lib.RSR_MAX_WINDOW:
+        raise ValueError(f"rs_reversal_replay: window in 1..{_lib.RSR_MAX_WINDOW}")
+    if not 0.0 <= float(par["quantile"]) <= 1.0:
+        raise ValueError("rs_reversal_replay: quantile in [0, 1]")
+    columns = tuple(columns)
+    _replay_columns("rs_reversal_replay", columns, _lib.RSR_VALUES)
+    S, T = _replay_shape(volume)
+    _replay_panels([(volume, "volume")], S, T)
+    mk = _replay_regime(market_regime, "market_regime", ((1,), (T,)))
+    if mk is None:
+        raise ValueError("market_regime: expected an int8 tensor of shape (1,) or (T,) (negative codes: None)")
+    Tc = int(mk.numel())
+    if (not isinstance(average_return, torch.Tensor) or average_return.dtype != torch.float64
+            or tuple(average_return.shape) != (Tc,)):
+        raise ValueError(f"average_return: expected a float64 tensor of shape {(Tc,)}")
+    if context_ok is not None and (not isinstance(context_ok, torch.Tensor)
+                                   or context_ok.dtype not in (torch.bool, torch.uint8)
+                                   or tuple(context_ok.shape) != (Tc,)):
+        raise ValueError(f"context_ok: expected a bool / uint8 tensor of shape {(Tc,)}")
+    flags = (torch.bool, torch.uint8)
+    if features_ok is None:
+        (rsv,), ld_sym = _replay_sym((rs,), (("relative_strength_vs_btc", (torch.float64,)),), S, T)
+        fok = None
+    else:
+        (fok, rsv), ld_sym = _replay_sym((features_ok, rs), (("features_ok", flags),
+                                                             ("relative_strength_vs_btc", (torch.float64,))), S, T)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    vv = _check_panel(volume, "volume")
+    _replay_on_device("context_ok / market_regime / average_return / features_ok / relative_strength_vs_btc",
+                      [context_ok, mk, average_return, fok, rsv])
+    cok = context_ok.contiguous() if context_ok is not None else None
+    mk, ar = mk.contiguous(), average_return.contiguous()
+    dev = volume.device
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqRsReversalParams, par, _RSR_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.RSR_VALUES, S, T, dev)
+    st = _lib.load().bq_rs_reversal_replay(
+        _ptr(vv), _row_stride(vv), _ptr(cok), _ptr(mk), _ptr(ar), Tc, _ptr(fok), _ptr(rsv), ld_sym, _ptr(lens),
+        _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_rs_reversal_replay")
     return status, outs
 
 

@@ -64,6 +64,12 @@ prefix frame df.iloc[:t + 1]:
                      the prior-close / EMA20 reclaim, one pass (bq_dip.hip),
                      with buy_the_dip_routing for the message's autotrade flag
                      and route (:87-125)
+* rs_reversal_entry  the decisions of RelativeStrengthReversalRange.signal()
+                     (strategies/relative_strength_reversal_range.py:56-101)
+                     on the 15m frame: the frame gate, regime_routing and
+                     the 24 h volume floor (Series.quantile, sorted only
+                     where a candle passes the route), one pass
+                     (bq_rsreversal.hip)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -1311,3 +1317,46 @@ def bb_extreme_routing(context_ok, regime_is_transitioning, timestamp, regime_st
         refused = refused | cond
     res = F.run({"route": _first_code(refusals, base), "autotrade": ~refused}, S, T)
     return res["autotrade"], res["route"].to(torch.uint8)
+
+
+# ---- the contrarian long on a relative-strength leader in a weak RANGE market: RelativeStrengthReversalRange ---------
+# bq_rs_reversal_replay's status codes: where RelativeStrengthReversalRange.signal() returned, in the method's order
+# (3-8: regime_routing's reasons; the others are this library's names)
+(RSR_EMIT, RSR_NO_FRAME, RSR_SHORT_FRAME, RSR_NO_CONTEXT, RSR_REGIME_NONE, RSR_NOT_RANGE, RSR_MARKET_NOT_WEAK,
+ RSR_NO_FEATURES, RSR_RS_INSUFFICIENT, RSR_DEAD_TAPE) = range(10)
+RSR_REASONS = dict(enumerate(_lib.RSR_REASONS))
+RSR_VALUES = _lib.RSR_VALUES
+RSR_ROUTE = "range_rs_reversal"   # the route of every emitted message; autotrade is always False
+
+
+def rs_reversal_entry(volume, context_ok, market_regime, average_return, features_ok, rs, *, first_t=None, lens=None,
+                      from_t=None, columns=RSR_VALUES, **params):
+    """The decisions of RelativeStrengthReversalRange.signal() (strategies/
+    relative_strength_reversal_range.py:75-101 with regime_routing :56-73) for
+    every candle of a 15m panel in one pass (engine.rs_reversal_replay,
+    bq_rs_reversal_replay). Column t of row s = the method on the message
+    whose frame is df.iloc[first_t[s]:t + 1]; candles from_t[s] .. lens[s] - 1
+    are replayed. The method keeps no state: a column does not depend on
+    earlier messages. volume [S, T] float64. The context of candle t's
+    message, [1] (one context for every candle) or [T]: context_ok bool /
+    uint8 (None: present), market_regime int8 (_lib.MARKET_REGIMES codes,
+    negative: None), average_return float64. The symbol's entry in the
+    context's snapshot, [S] or [S, T]: features_ok bool / uint8 (None:
+    present) and rs, its relative_strength_vs_btc. The volume floor is
+    df["volume"].tail(window).quantile(quantile): Series.quantile, numpy's
+    linear percentile with its two-sided lerp over the non-NaN rows, +-inf a
+    value: not pandas' rolling quantile (a one-sided lerp, +-inf missing),
+    which gives another number on many windows. A finite rank
+    beside an infinite one gives a NaN floor, and the method emits. The floor
+    sits behind the route gate, so the pass sorts only in the 64-candle steps
+    where a candle passes it. params: engine.RS_REVERSAL_DEFAULTS' keys.
+
+    Returns {"status": uint8 [S, T] (RSR_* codes, RSR_REASONS their names; 0 =
+    the message goes out), and the `columns` of RSR_VALUES, float64 [S, T]}:
+    volume_floor, NaN where the method did not reach it (status 1-8). The
+    message always carries autotrade=False and the route RSR_ROUTE, so there
+    is no routing function; its text, quote_asset_volume and the dispatch stay
+    host steps."""
+    status, vals = engine.rs_reversal_replay(volume, context_ok, market_regime, average_return, features_ok, rs,
+                                             first_t=first_t, lens=lens, from_t=from_t, columns=columns, **params)
+    return {"status": status, **vals}

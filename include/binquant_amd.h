@@ -72,6 +72,10 @@
  *                         _compute_rsi with pandas' roll_mean over the frame's last
  *                         30 closes, evaluate's band position and the two extremes
  *                         (strategies/coinrule/bb_extreme_reversion.py:134-285)
+ *   bq_rs_reversal_replay <- RelativeStrengthReversalRange.signal(): the frame gate,
+ *                         regime_routing and the 24 h volume floor, Series.quantile
+ *                         over the frame's last 96 volumes
+ *                         (strategies/relative_strength_reversal_range.py:56-101)
  *   bq_top_gainer_entry <- TopGainerEarlyMomentum._features / _entry_allows and
  *                         signal()'s two-close confirmation
  *                         (strategies/top_gainer_early_momentum.py:91-253, :363-406)
@@ -993,6 +997,74 @@ int bq_bb_extreme_replay(const double* close, int64_t ld_px, const double* bb_up
                          uint8_t* status, double* const* values, int64_t ld_out, void* stream);
 
 /*
+ * RelativeStrengthReversalRange.signal() replayed over a panel of 15m frames
+ * (strategies/relative_strength_reversal_range.py:75-101, with regime_routing
+ * :56-73): column t of row s is what signal() does on the message whose frame
+ * is df.iloc[first:t + 1], first = first_t[s] (NULL: 0). The method keeps no
+ * state: a column does not depend on the messages before it. Candles t =
+ * max(from_t[s], first) (from_t NULL: 0) .. lens[s] - 1 (NULL: T) are replayed.
+ * volume [S][ld_v]. The context of candle t's message: context_ok (NULL: a
+ * context is present), market_regime (int8, an index into "TREND_UP",
+ * "TREND_DOWN", "RANGE", "HIGH_STRESS", "TRANSITIONAL"; negative: None) and
+ * average_return, each of length ctx_T, 1 (one context for every candle) or T.
+ * The symbol's entry in the context's snapshot: features_ok (NULL: present;
+ * false: the context has no features for the symbol) and
+ * relative_strength_vs_btc, [S] with ld_sym 0, or [S][ld_sym] per candle.
+ *
+ * Per candle, in the method's order (the first match wins):
+ *   # condition                                          status            lines
+ *   1 t outside [max(from_t, first), lens)               NO_FRAME
+ *   2 t + 1 - first < window                             SHORT_FRAME       :85
+ *   3 context_ok false                                   NO_CONTEXT        :61
+ *   4 market_regime < 0                                  REGIME_NONE       :63
+ *   5 market_regime != RANGE                             NOT_RANGE         :65
+ *   6 average_return >= avg_return_max (a NaN goes on)   MARKET_NOT_WEAK   :67
+ *   7 features_ok false                                  NO_FEATURES       :69
+ *   8 relative_strength_vs_btc <= rs_min (a NaN goes on) RS_INSUFFICIENT   :71
+ *   9 volume[t] <= volume_floor (a NaN on either side    DEAD_TAPE         :100
+ *     goes on)
+ *   0 otherwise                                          EMIT
+ * volume_floor = df["volume"].tail(window).quantile(quantile), which is
+ * Series.quantile, np.percentile(method="linear") over the non-NaN rows, not
+ * pandas' rolling quantile: +-inf is a value; with s the n non-NaN values of
+ * volume[t - window + 1 .. t] ascending (n == 0: NaN), vi = (n - 1) * quantile
+ * (the quantile after pandas' and numpy's round trip, (quantile * 100) / 100),
+ * fl = floor(vi), g = vi - fl, a = s[fl], b = s[min(fl + 1, n - 1)], d = b - a,
+ * the floor is b - d * (1 - g) where g >= 0.5 and a + d * g otherwise, without
+ * FMA and also where g == 0: a finite a beside an infinite b gives NaN, and
+ * the message goes out. The floor of a zero is +0.0 or -0.0. The message
+ * always carries autotrade = False and the route "range_rs_reversal"; its
+ * text, quote_asset_volume and the dispatch are the caller's.
+ *
+ * status [S][ld_out] bytes (BQ_RSR_*), values: NULL or BQ_RSR_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_RSR_V_* order:
+ * volume_floor, NaN for status 1-8. params NULL: bq_rs_reversal_default_params.
+ * BQ_EINVAL, before any launch, unless every ld >= T (ld_sym: or 0), ctx_T is 1
+ * or T, 1 <= window <= BQ_RSR_MAX_WINDOW (window + 63 <= 256 sorted slots),
+ * 0 <= quantile <= 1 and the two thresholds are finite. S == 0 or T == 0: BQ_OK.
+ */
+#define BQ_RSR_MAX_WINDOW 192
+#define BQ_RSR_NVALUES 1
+#define BQ_RSR_REGIME_RANGE 2   /* market_regime "RANGE" */
+typedef struct bq_rs_reversal_params {
+  int32_t window;          /* 96    VOLUME_WINDOW */
+  int32_t reserved;
+  double quantile;         /* 0.20  VOLUME_PERCENTILE */
+  double avg_return_max;   /* -0.02 AVG_RETURN_MAX */
+  double rs_min;           /* 0.05  RS_VS_BTC_MIN */
+} bq_rs_reversal_params;
+enum { BQ_RSR_EMIT = 0, BQ_RSR_NO_FRAME, BQ_RSR_SHORT_FRAME, BQ_RSR_NO_CONTEXT, BQ_RSR_REGIME_NONE, BQ_RSR_NOT_RANGE,
+       BQ_RSR_MARKET_NOT_WEAK, BQ_RSR_NO_FEATURES, BQ_RSR_RS_INSUFFICIENT, BQ_RSR_DEAD_TAPE };
+enum { BQ_RSR_V_FLOOR = 0 };
+void bq_rs_reversal_default_params(bq_rs_reversal_params* p);
+int bq_rs_reversal_replay(const double* volume, int64_t ld_v, const uint8_t* context_ok, const int8_t* market_regime,
+                          const double* average_return, int64_t ctx_T, const uint8_t* features_ok,
+                          const double* relative_strength_vs_btc, int64_t ld_sym, const int64_t* lens,
+                          const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
+                          const bq_rs_reversal_params* params, uint8_t* status, double* const* values,
+                          int64_t ld_out, void* stream);
+
+/*
  * RelativeStrengthImpulseRider._features at every prefix t
  * (strategies/relative_strength_impulse_rider.py:92-198, with _btc_return_at,
  * :69-90): column t of row s is the method on df.iloc[first:t + 1], first =
@@ -1387,8 +1459,10 @@ int bq_pump_ewm(const double* high, const double* low, const double* close, int6
  * out[s] = numpy.quantile(x[s][~isnan], q) (numpy 'linear' method, numpy's
  * two-sided lerp), NaN for a row without observations. Replaces the
  * np.quantile calls of FailedSpikeFade.auto_calibrate
- * (strategies/failed_spike_fade.py:229-257) and Series.quantile
- * (strategies/relative_strength_reversal_range.py:98). out: S doubles.
+ * (strategies/failed_spike_fade.py:229-257). One number per row, for the
+ * row's newest candle alone: the volume floor of
+ * RelativeStrengthReversalRange.signal() at every candle, behind its route
+ * gate, is bq_rs_reversal_replay's (the same index and lerp). out: S doubles.
  */
 int bq_row_quantile(const double* x, int64_t S, int64_t T, int64_t ld_in, double q, double* out, void* stream);
 
