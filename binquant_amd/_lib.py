@@ -216,6 +216,32 @@ class BqSpikeFadeParams(ctypes.Structure):
     _fields_ = [("window_bars", ctypes.c_int32), ("ext_factor", ctypes.c_double)]
 
 
+class BqSpikeFramesParams(ctypes.Structure):
+    """Mirror of ``bq_spike_frames_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("volume_cluster_window", ctypes.c_int32), ("volume_cluster_min_count", ctypes.c_int32),
+                ("cumulative_price_window", ctypes.c_int32), ("label_mode", ctypes.c_int32),
+                ("require_both_patterns", ctypes.c_int32), ("require_bullish_spike", ctypes.c_int32),
+                ("post_spike_cooldown_bars", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("cumulative_price_threshold", ctypes.c_double), ("body_size_pct_min", ctypes.c_double),
+                ("volume_cluster_min_ratio", ctypes.c_double), ("price_break_base_threshold", ctypes.c_double),
+                ("volume_quantile", ctypes.c_double), ("price_base_floor_quantile", ctypes.c_double),
+                ("min_volume_ratio", ctypes.c_double), ("min_price_abs_floor", ctypes.c_double)]
+
+
+# bq_spike_frames: the caps (BQ_SPIKE_FRAMES_MAX_*), the input columns (enum bq_spike_frames_in / _in_b) and the
+# byte outputs (enum bq_spike_frames_out) under their detect() / latest_signal() names
+SPIKE_FRAMES_MAX_T = 2048
+SPIKE_FRAMES_MAX_WINDOW = 30
+SPIKE_FRAMES_MAX_COOLDOWN = 64
+SPIKE_FRAMES_IN = ("volume_ratio", "price_change_abs", "dyn_threshold", "body_size_pct", "cum_pos", "cum_neg", "open",
+                   "close")
+SPIKE_FRAMES_IN_B = ("accel_spike_flag", "accel_spike_short_flag", "upward", "downward")
+SPIKE_FRAMES_OUT = ("label", "label_pre", "label_short", "label_short_pre", "volume_cluster_flag", "price_break_flag",
+                    "cumulative_price_break_flag", "cumulative_price_break_short_flag", "accel_spike_flag",
+                    "accel_spike_short_flag", "upward", "downward")
+
+
 # bq_spike_fade_replay: event codes (BQ_FS_*), detail bits (BQ_FS_D_*)
 SPIKEFADE_MAX_WINDOW = 32
 (BQ_FS_IDLE, BQ_FS_SOURCE_SET, BQ_FS_WAITING, BQ_FS_CANDIDATE, BQ_FS_CLEARED, BQ_FS_SAME_CANDLE) = range(6)
@@ -472,6 +498,11 @@ SIGNATURES: dict[str, tuple] = {
     "bq_spike_fade_default_params": (None, [ctypes.POINTER(BqSpikeFadeParams)]),
     "bq_spike_fade_replay": (ctypes.c_int, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _I64,
                                             ctypes.POINTER(BqSpikeFadeParams), _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "bq_spike_frames_default_params": (None, [ctypes.POINTER(BqSpikeFramesParams)]),
+    "bq_spike_frames_workspace": (ctypes.c_size_t, [_I64, _I64]),
+    "bq_spike_frames": (ctypes.c_int, [_PP, _I64, _PP, _I64, _I32, _P, _P, _P, _I64, _I64,
+                                       ctypes.POINTER(BqSpikeFramesParams), _P, ctypes.c_size_t, _P, _P, _PP, _I64,
+                                       _P]),
     "bq_price_tracker_default_params": (None, [ctypes.POINTER(BqPriceTrackerParams)]),
     "bq_price_tracker_replay": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64,
                                                _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64,

@@ -38,6 +38,29 @@ __device__ __forceinline__ double key_value(uint64_t k) {
   return __longlong_as_double((long long)u);
 }
 
+// numpy.quantile's default 'linear' method on n >= 1 sorted observations
+// (numpy/lib/_function_base_impl.py _quantile, numpy 2.2): the virtual index
+// (n - 1) q, previous = floor, next = previous + 1 clamped to n - 1, gamma =
+// index - previous, and numpy's two-sided _lerp of the two order statistics.
+// Shared by bq_row_quantile and bq_spike_frames: one arithmetic, one set of bits.
+struct QuantilePos {
+  int prev, next;
+  double gamma;
+};
+__device__ __forceinline__ QuantilePos quantile_pos(int n, double q) {
+  const double vi = (double)(n - 1) * q;
+  const double fl = floor(vi);
+  QuantilePos p;
+  p.prev = (int)fl;
+  p.next = p.prev + 1 < n ? p.prev + 1 : n - 1;
+  p.gamma = vi - fl;
+  return p;
+}
+__device__ __forceinline__ double quantile_lerp(double a, double b, double gamma) {
+  const double d = b - a;
+  return gamma >= 0.5 ? b - d * (1.0 - gamma) : a + d * gamma;
+}
+
 // ---- compensated (double-double) accumulation ------------------------------
 struct dd {
   double hi, lo;

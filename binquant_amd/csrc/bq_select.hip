@@ -101,11 +101,9 @@ __global__ __launch_bounds__(SQ_NT) void row_quantile_kernel(const double* __res
     if (tid == 0) out[blockIdx.x] = qnan();
     return;
   }
-  const double vi = (double)(n - 1) * q;
-  const double fl = floor(vi);
-  const int prev = (int)fl;
-  const int next = prev + 1 < n ? prev + 1 : n - 1;
-  const double gamma = vi - fl;
+  const QuantilePos qpos = quantile_pos(n, q);
+  const int prev = qpos.prev, next = qpos.next;
+  const double gamma = qpos.gamma;
 
   // radix select of the prev-th smallest key
   uint64_t prefix = 0, mask = 0;
@@ -200,10 +198,7 @@ __global__ __launch_bounds__(SQ_NT) void row_quantile_kernel(const double* __res
     const uint64_t mn = block_min_u64(above, red_u);
     b = nle > next ? a : key_value(mn);
   }
-  if (tid == 0) {
-    const double d = b - a;
-    out[blockIdx.x] = gamma >= 0.5 ? b - d * (1.0 - gamma) : a + d * gamma;
-  }
+  if (tid == 0) out[blockIdx.x] = quantile_lerp(a, b, gamma);
 }
 
 // Rows of up to 64 * RQ_KW values: one WAVE per row (4 rows per workgroup),
@@ -260,11 +255,9 @@ __global__ __launch_bounds__(RQ_WPB * WAVE) void row_quantile_wave_kernel(const 
     if (lane == 0) out[row] = qnan();
     return;
   }
-  const double vi = (double)(n - 1) * q;
-  const double fl = floor(vi);
-  const int prev = (int)fl;
-  const int next = prev + 1 < n ? prev + 1 : n - 1;
-  const double gamma = vi - fl;
+  const QuantilePos qpos = quantile_pos(n, q);
+  const int prev = qpos.prev, next = qpos.next;
+  const double gamma = qpos.gamma;
   uint64_t prefix = 0, mask = 0;
   int k = prev;
   for (int sh = 56; sh >= 0; sh -= 8) {
@@ -351,10 +344,7 @@ __global__ __launch_bounds__(RQ_WPB * WAVE) void row_quantile_wave_kernel(const 
     }
     b = le > next ? a : key_value(above);
   }
-  if (lane == 0) {
-    const double d = b - a;
-    out[row] = gamma >= 0.5 ? b - d * (1.0 - gamma) : a + d * gamma;
-  }
+  if (lane == 0) out[row] = quantile_lerp(a, b, gamma);
 }
 
 // One wave per symbol row: 64 candles per step are read as one coalesced

@@ -1956,6 +1956,101 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
     return event, det, brs
 
 
+SPIKE_FRAME_FLOAT = ("volume_cluster_min_ratio", "price_break_base_threshold")
+SPIKE_FRAME_COLUMNS = _lib.SPIKE_FRAMES_OUT + SPIKE_FRAME_FLOAT
+SPIKE_FRAMES_MAX_T = _lib.SPIKE_FRAMES_MAX_T   # candles per panel row: a frame's sorted prefix lives in LDS
+
+
+def spike_frames_params(params) -> "_lib.BqSpikeFramesParams":
+    """bq_spike_frames_params from a strategies.SpikeParams (or any object with
+    its attributes), checked against the kernel's range: ValueError outside it."""
+    mode = getattr(params, "volume_cluster_label_mode", "last")
+    if mode not in _SPIKE_MODES:
+        raise ValueError(f"spike_frames: volume_cluster_label_mode must be one of {sorted(_SPIKE_MODES)}, got {mode!r}")
+    vw, cw = int(params.volume_cluster_window), int(params.cumulative_price_window)
+    bars = int(params.post_spike_cooldown_bars)
+    if not 1 <= vw <= _lib.SPIKE_FRAMES_MAX_WINDOW:
+        raise ValueError(f"spike_frames: volume_cluster_window must be in 1..{_lib.SPIKE_FRAMES_MAX_WINDOW}, got {vw}")
+    if not 2 <= cw <= _lib.SPIKE_FRAMES_MAX_WINDOW:
+        raise ValueError(f"spike_frames: cumulative_price_window must be in 2..{_lib.SPIKE_FRAMES_MAX_WINDOW}, "
+                         f"got {cw}")
+    if bars >= _lib.SPIKE_FRAMES_MAX_COOLDOWN:
+        raise ValueError(f"spike_frames: post_spike_cooldown_bars must be below {_lib.SPIKE_FRAMES_MAX_COOLDOWN} "
+                         f"(the cooldown walk scans 64-candle masks), got {bars}")
+    if int(params.volume_cluster_min_count) < 0:
+        raise ValueError("spike_frames: volume_cluster_min_count must not be negative")
+    floats = {k: float(getattr(params, k)) for k in (
+        "cumulative_price_threshold", "body_size_pct_min", "volume_cluster_min_ratio", "price_break_base_threshold",
+        "volume_quantile", "price_base_floor_quantile", "min_volume_ratio", "min_price_abs_floor")}
+    for k, val in floats.items():
+        if not math.isfinite(val):
+            raise ValueError(f"spike_frames: {k} must be finite, got {val}")
+    for k in ("volume_quantile", "price_base_floor_quantile"):
+        if not 0.0 <= floats[k] <= 1.0:
+            raise ValueError(f"spike_frames: {k} must lie in [0, 1], got {floats[k]}")
+    return _lib.BqSpikeFramesParams(vw, int(params.volume_cluster_min_count), cw, _SPIKE_MODES[mode],
+                                    int(bool(params.require_both_patterns)), int(bool(params.require_bullish_spike)),
+                                    bars, 0, *floats.values())
+
+
+@device_entry
+def spike_frames(cols: dict, params, *, first_t=None, lens=None, from_t=None, aligned: bool = False,
+                 columns=SPIKE_FRAME_COLUMNS) -> dict[str, torch.Tensor]:
+    """FailedSpikeFade.latest_signal() of every frame of a row
+    (strategies/failed_spike_fade.py:229-594; bq_spike_frames): column t of
+    row s = the method on a fresh instance whose frame is
+    df.iloc[first_t[s]:t + 1] (RangeIndex); candles max(from_t[s],
+    first_t[s]) .. lens[s] - 1 are formed. cols: the threshold-independent
+    columns of detect(), float64 [S, T] under _lib.SPIKE_FRAMES_IN's names
+    (volume_ratio, price_change_abs, dyn_threshold: the forward-filled rolling
+    quantile, body_size_pct, cum_pos / cum_neg: the rolling sums of the clipped
+    price changes, open, close) and bool [S, T] under _lib.SPIKE_FRAMES_IN_B's
+    (the two acceleration flags, upward, downward), each as a frame starting
+    at first_t forms it. aligned: column j of an input row holds candle
+    first_t[s] + j. params: strategies.SpikeParams. T <= SPIKE_FRAMES_MAX_T
+    (the expanding quantile keeps a frame's sorted prefix in LDS): a longer
+    panel raises ValueError. Returns {name: [S, T]} for `columns`
+    (SPIKE_FRAME_COLUMNS: latest_signal()'s flags as bool, the two calibrated
+    thresholds as float64); False / NaN outside the formed candles. Allocates
+    by shape, reads nothing back."""
+    _replay_columns("spike_frames", columns, SPIKE_FRAME_COLUMNS)
+    p = spike_frames_params(params)
+    missing = [k for k in _lib.SPIKE_FRAMES_IN + _lib.SPIKE_FRAMES_IN_B if k not in cols]
+    if missing:
+        raise ValueError(f"spike_frames: missing input columns {missing}")
+    S, T = _replay_shape(cols["close"])
+    if T > SPIKE_FRAMES_MAX_T:
+        raise ValueError(f"spike_frames: T = {T} exceeds the cap of {SPIKE_FRAMES_MAX_T} candles per row")
+    fin = [(cols[k], k) for k in _lib.SPIKE_FRAMES_IN]
+    _replay_panels(fin, S, T)
+    for k in _lib.SPIKE_FRAMES_IN_B:
+        x = cols[k]
+        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.bool, torch.uint8) or tuple(x.shape) != (S, T):
+            raise ValueError(f"{k}: expected a bool tensor of shape {(S, T)}")
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    fcols, ld_in = _common_pitch([_check_panel(x, n) for x, n in fin])
+    bcols = [cols[k] for k in _lib.SPIKE_FRAMES_IN_B]
+    _replay_on_device("spike_frames: flag inputs", bcols)
+    if any(T > 1 and x.stride(1) != 1 for x in bcols):
+        bcols = [x.contiguous() for x in bcols]
+    bcols, ld_b = _common_pitch(bcols)
+    dev = fcols[0].device
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    out = {k: torch.empty((S, T), dtype=torch.float64 if k in SPIKE_FRAME_FLOAT else torch.bool, device=dev)
+           for k in SPIKE_FRAME_COLUMNS if k in columns}
+    lib = _lib.load()
+    nbytes = int(lib.bq_spike_frames_workspace(S, T))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    st = lib.bq_spike_frames(
+        _lib.ptr_array([x.data_ptr() for x in fcols]), ld_in, _lib.ptr_array([x.data_ptr() for x in bcols]), ld_b,
+        int(bool(aligned)), _ptr(lens), _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(ws), nbytes,
+        _ptr(out.get("volume_cluster_min_ratio")), _ptr(out.get("price_break_base_threshold")),
+        _lib.ptr_array([out[k].data_ptr() if k in out else 0 for k in _lib.SPIKE_FRAMES_OUT]), T,
+        _stream_handle(None))
+    _lib.check(st, "bq_spike_frames")
+    return out
+
+
 PRICE_TRACKER_DEFAULTS = dict(   # PriceTracker.signal()'s constants and class attributes (:34-35, :59-63, :177-239)
     min_history=30, tail_rows=5, span_fast=9, span_slow=21, rsi_max=30.0, macd_max=0.0, mfi_max=20.0, w_rsi=0.35,
     w_mfi=0.35, w_macd=0.3, macd_scale=100.0, context_weight=0.35, risk_weight=0.35, support_weight=0.2,

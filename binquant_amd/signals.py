@@ -45,7 +45,8 @@ prefix frame df.iloc[:t + 1]:
 * failed_spike_fade  the body of FailedSpikeFade.signal()
                      (strategies/failed_spike_fade.py:596-695): the pending-spike
                      state machine replayed per row (bq_spikefade.hip), with
-                     spike_source_allows (:190-203) and
+                     spike_source_allows (:190-203), spike_source_frames
+                     (that gate on the frame ending at every candle) and
                      spike_fade_market_allows (:155-188)
 * price_tracker_entry  the decisions of PriceTracker.signal()
                      (strategies/coinrule/price_tracker.py:165-251) on the 5m
@@ -465,6 +466,24 @@ def spike_source_allows(label, price_break_flag, cumulative_price_break_flag, ac
     return reason == 0, reason
 
 
+def spike_source_frames(o, h, l, c, v, qv, p=None, *, first_t=None, lens=None, from_t=None, exact: bool = True,
+                        max_candle_return: float = 0.06):
+    """FailedSpikeFade.source_spike_allows on the message of EVERY candle:
+    spike_source_allows over strategies.failed_spike_frames' columns, column t
+    of row s from latest_signal() of a fresh instance on the frame
+    df.iloc[first_t[s]:t + 1]. Returns (ok bool [S, T], reason uint8 [S, T]),
+    ok ready for failed_spike_fade(source_ok=...); outside the formed candles
+    ok is False (reason 1: no label there). p: strategies.SpikeParams; the
+    other arguments are failed_spike_frames'."""
+    from . import strategies
+
+    f = strategies.failed_spike_frames(o, h, l, c, v, qv, p, first_t=first_t, lens=lens, from_t=from_t, exact=exact,
+                                       columns=("label", "price_break_flag", "cumulative_price_break_flag",
+                                                "accel_spike_flag", "close_open_ratio", "upward"))
+    return spike_source_allows(f["label"], f["price_break_flag"], f["cumulative_price_break_flag"],
+                               f["accel_spike_flag"], f["close_open_ratio"], f["upward"], max_candle_return)
+
+
 def spike_fade_market_allows(market_stress_score, long_regime_score, short_regime_score, context_ok, momentum_points,
                              max_market_stress: float = 0.35, min_momentum: float = 0.5):
     """FailedSpikeFade.source_market_allows / failure_market_allows
@@ -500,10 +519,12 @@ def failed_spike_fade(o, h, c, open_time, source_ok, *, src_market=None, fail_ma
     source_ok [S, T] bool: column t must hold source_spike_allows of the
     FRAME ENDING AT t (spike_source_allows on the newest column of
     strategies.failed_spike_features of that frame). The cohort's newest
-    column is exactly that. A whole-row failed_spike_features over a long
-    panel is an approximation of it: detect()'s auto-calibration and cooldown
-    are frame-wide, so an earlier column of a long frame is not what the
-    message at that candle saw. The caller chooses. src_market / fail_market:
+    column is exactly that, and spike_source_frames forms it for every
+    candle of a panel in about one pass (strategies.failed_spike_frames: the
+    per-prefix detect()). A whole-row failed_spike_features over a long panel
+    is NOT it: detect()'s auto-calibration and cooldown are frame-wide, so an
+    earlier column of a long frame is not what the message at that candle
+    saw. src_market / fail_market:
     spike_fade_market_allows' source_ok / failure_ok, bool [T] or [S, T]
     (None: allowed). params: engine.SPIKE_FADE_DEFAULTS' keys.
 

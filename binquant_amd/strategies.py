@@ -7,6 +7,9 @@
 * failed_spike_features — FailedSpikeFade.detect
   (strategies/failed_spike_fade.py:533-544): base / early features, the
   whole-series auto-calibration, labels, cooldown and streaks.
+* failed_spike_frames — FailedSpikeFade.latest_signal (:546-594) of a fresh
+  instance on EVERY frame df.iloc[first:t + 1] of a row: the expanding
+  auto-calibration and the cooldown walk per candle (bq_spikeframes.hip).
 
 Each pipeline is a few stages: the order statistics, recurrences and
 forward fills run in the kernels of bq_rolling.hip (rolling median / quantile
@@ -597,3 +600,119 @@ def failed_spike_features(o, h, l, c, v, qv, p: SpikeParams | None = None,
     out["upward"] = f["upward"]
     out["downward"] = f["downward"]
     return out
+
+
+# failed_spike_frames' columns: FailedSpikeFade.latest_signal()'s flags (:570-594), close_open_ratio and the
+# instance's two calibrated thresholds after the call
+SPIKE_FRAME_KEYS = engine.SPIKE_FRAME_COLUMNS + ("close_open_ratio",)
+
+
+def _frame_aligned(x: torch.Tensor, first_t: torch.Tensor) -> torch.Tensor:
+    """Row s shifted left by first_t[s]: column j holds candle first_t[s] + j (NaN past the row's end)."""
+    S, T = x.shape
+    idx = first_t.reshape(S, 1).clamp(0, T) + torch.arange(T, device=x.device).reshape(1, T)
+    return torch.where(idx < T, torch.gather(x, 1, idx.clamp(max=T - 1)), torch.full_like(x, NAN))
+
+
+def spike_frame_columns(o, c, v, p: SpikeParams | None = None, exact: bool = True) -> dict[str, torch.Tensor]:
+    """engine.spike_frames' inputs from contiguous [S, T] open / close /
+    volume panels whose frames start at column 0: the columns of
+    FailedSpikeFade.detect() that no calibrated threshold enters
+    (_lib.SPIKE_FRAMES_IN / SPIKE_FRAMES_IN_B's names) and close_open_ratio.
+    The close's ffill, two fused element-wise programs around one batched
+    rolling call, the acceleration flags and the quantile's ffill."""
+    p = p or SpikeParams()
+    eps = 1e-6
+    S, T = c.shape
+    w, n, aw, cw = int(p.base_window), int(p.streak_length), int(p.accel_volume_deriv_window), \
+        int(p.cumulative_price_window)
+    O, C, V = F.inp(o), F.inp(c), F.inp(v)
+    # ---- compute_base_features (:260-322), the operands of the rolling columns ----
+    (cf,) = engine.rolling_many(FF(c))
+    pc = pct_change_filled(cf, 1)
+    b = F.run({"price_change": pc, "price_change_abs": pc.abs(), "body_size_pct": (C - O).abs() / (O + eps),
+               "close_open_ratio": (C - O) / (O + eps), "_green": (C > O).float(), "_red": (C < O).float(),
+               "_clip_pos": F.clip_lower(pc, 0.0), "_neg": F.where(pc > 0, 0.0, pc).abs()})
+    volume_ma, green, red, cum_pos, cum_neg, dyn = engine.rolling_many(
+        R(v, w, "mean"), R(b["_green"], n, "isum"), R(b["_red"], n, "isum"), R(b["_clip_pos"], cw, "sum"),
+        R(b["_neg"], cw, "sum"), R(b["price_change_abs"], 60, "quantile", q=p.price_break_dynamic_q, min_periods=20),
+        exact=exact)
+    m = F.run({"volume_ratio": V / (F.inp(volume_ma) + eps), "upward": F.inp(green) >= n,
+               "downward": F.inp(red) >= n})
+    # ---- acceleration_flag (:423-444): no calibrated threshold in it ----
+    VR, PCA, PC = F.inp(m["volume_ratio"]), F.inp(b["price_change_abs"]), F.inp(b["price_change"])
+    acc = ((VR - F.shift(VR, aw)) >= p.accel_volume_deriv_min) & (PCA >= p.accel_price_change_min)
+    a = F.run({"accel_spike_flag": acc & (PC > 0), "accel_spike_short_flag": acc & (PC < 0)}, S, T)
+    (dyn_ff,) = engine.rolling_many(FF(dyn))   # max(floor, dyn).ffill() == max(floor, ffill(dyn)) (:395-398)
+    return {"volume_ratio": m["volume_ratio"], "price_change_abs": b["price_change_abs"], "dyn_threshold": dyn_ff,
+            "body_size_pct": b["body_size_pct"], "cum_pos": cum_pos, "cum_neg": cum_neg, "open": o, "close": c,
+            "accel_spike_flag": a["accel_spike_flag"], "accel_spike_short_flag": a["accel_spike_short_flag"],
+            "upward": m["upward"], "downward": m["downward"], "close_open_ratio": b["close_open_ratio"]}
+
+
+def failed_spike_frames(o, h, l, c, v, qv, p: SpikeParams | None = None, *, first_t=None, lens=None, from_t=None,
+                        exact: bool = True, columns=SPIKE_FRAME_KEYS) -> dict[str, torch.Tensor]:
+    """FailedSpikeFade.latest_signal() at EVERY candle of an [S, T] panel:
+    column t of row s = the method on a fresh instance (the live behaviour: a
+    new strategy instance per message, so the price floor is no running
+    maximum) whose frame is df.iloc[first_t[s]:t + 1] with a RangeIndex, t <
+    lens[s]; candles max(from_t[s], first_t[s]) .. lens[s] - 1 are formed. The
+    rolling warm-up starts at first_t[s]. This is the frame-exact source gate
+    of signals.failed_spike_fade; failed_spike_features over the same panel
+    gives the LAST frame's columns (auto_calibrate and apply_cooldown look at
+    the whole frame) and differs from it on earlier candles.
+
+    The threshold-independent columns are formed once per row with the
+    existing passes (spike_frame_columns: the close's ffill, fused
+    element-wise programs, one batched rolling call), frame-aligned by one gather per input when first_t
+    is given; engine.spike_frames (bq_spike_frames) then forms, per candle,
+    the expanding np.quantile calibration (skipped, leaving the defaults 1.6 /
+    0.03, while volume_ratio or price_change_abs has no observation in the
+    frame: frames shorter than base_window rows, all-NaN frames), the flags
+    under it and the cooldown walk. exact=True: the rolling mean / sums by the
+    bit-exact replay of pandas (the thresholds then equal
+    failed_spike_features(frame, exact=True)'s bit for bit); False: the
+    time-parallel kernels, within rounding.
+
+    Returns {name: [S, T]} for `columns` (SPIKE_FRAME_KEYS): bool flags,
+    float64 close_open_ratio / volume_cluster_min_ratio /
+    price_break_base_threshold; False / NaN outside the formed candles (
+    close_open_ratio: wherever the candle is). Supported: the fused path's
+    SpikeParams range (windows <= 30, cumulative_price_window >= 2, the dynamic
+    price break, the three label modes), post_spike_cooldown_bars < 64, and T
+    <= engine.SPIKE_FRAMES_MAX_T candles (five times the live store's frame
+    cap); ValueError outside it. A sliding frame cap (a frame that starts
+    later as t grows) is not formed: every frame of a row starts at first_t.
+    Allocates by shape only and reads nothing back (graph-capturable)."""
+    p = p or SpikeParams()
+    unknown = [k for k in columns if k not in SPIKE_FRAME_KEYS]
+    if unknown:
+        raise ValueError(f"failed_spike_frames: unknown columns {unknown} (known: {SPIKE_FRAME_KEYS})")
+    engine.spike_frames_params(p)
+    if not p.price_break_use_dynamic:
+        raise ValueError("failed_spike_frames: price_break_use_dynamic=False is not supported")
+    w, n, aw = int(p.base_window), int(p.streak_length), int(p.accel_volume_deriv_window)
+    if not (1 <= w <= 30 and 1 <= n <= 30 and 1 <= aw <= 30):
+        raise ValueError(f"failed_spike_frames: base_window, streak_length and accel_volume_deriv_window must be in "
+                         f"1..30, got {(w, n, aw)}")
+    S, T = engine._replay_shape(c)
+    if T > engine.SPIKE_FRAMES_MAX_T:
+        raise ValueError(f"failed_spike_frames: T = {T} exceeds the cap of {engine.SPIKE_FRAMES_MAX_T} candles per row")
+    engine._replay_panels(((o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume"),
+                           (qv, "quote_asset_volume")), S, T)
+    lens, first_t, from_t = engine._replay_rows(lens, first_t, from_t, S)
+    o, c, v = (engine._check_panel(x, k).contiguous() for x, k in ((o, "open"), (c, "close"), (v, "volume")))
+    aligned = first_t is not None
+    if aligned:
+        first_t = first_t.to(device=c.device, dtype=torch.int64)
+        o, c, v = (_frame_aligned(x, first_t) for x in (o, c, v))
+    cols = spike_frame_columns(o, c, v, p, exact)
+    out = engine.spike_frames(cols, p, first_t=first_t, lens=lens, from_t=from_t, aligned=aligned,
+                              columns=tuple(k for k in columns if k != "close_open_ratio"))
+    if "close_open_ratio" in columns:
+        cor = cols["close_open_ratio"]
+        if aligned:   # back onto the panel's candles
+            idx = torch.arange(T, device=cor.device).reshape(1, T) - first_t.reshape(S, 1).clamp(0, T)
+            cor = torch.where(idx >= 0, torch.gather(cor, 1, idx.clamp(min=0)), torch.full_like(cor, NAN))
+        out["close_open_ratio"] = cor
+    return {k: out[k] for k in SPIKE_FRAME_KEYS if k in out}

@@ -53,6 +53,8 @@
  *                         (strategies/gradual_gainer_retest.py:222-308)
  *   bq_spike_fade_replay <- FailedSpikeFade.signal()'s pending-spike state machine
  *                         (strategies/failed_spike_fade.py:596-695)
+ *   bq_spike_frames    <- FailedSpikeFade.latest_signal() on every frame of a row, a fresh
+ *                         instance per frame (strategies/failed_spike_fade.py:229-594)
  *   bq_price_tracker_replay <- PriceTracker.signal(): the null gate, the oversold test,
  *                         the context score's rejections and the entry cooldown
  *                         (strategies/coinrule/price_tracker.py:83-99, :165-251)
@@ -481,6 +483,83 @@ int bq_spike_fade_replay(const double* open, const double* high, const double* c
                          const bq_spike_fade_params* params, uint8_t* st_active, int64_t* st_open_time,
                          double* st_high, double* st_close, uint8_t* event, uint8_t* detail, uint8_t* bars,
                          int64_t ld_out, void* stream);
+
+/*
+ * FailedSpikeFade.latest_signal() of every frame of a row
+ * (strategies/failed_spike_fade.py:229-594): column t of row s is the method
+ * on a FRESH instance (the live behaviour: one strategy instance per message)
+ * whose frame is df.iloc[first:t + 1], first = first_t[s] (NULL: 0), with a
+ * RangeIndex; candles t = max(from_t[s], first) (NULL: 0) .. lens[s] - 1
+ * (NULL: T) are formed. This is the source gate bq_spike_fade_replay's
+ * source_ok wants: auto_calibrate's two np.quantile calls (:229-257) and
+ * apply_cooldown's walk (:495-520) are frame-wide, so the columns of one
+ * whole-row detect() are those of the row's last frame only.
+ *
+ * in [BQ_NUM_SPIKE_FRAMES_IN] fp64 [S][ld_in]: the columns of detect() that do
+ * not depend on the calibrated thresholds, as a frame starting at `first`
+ * forms them (the rolling warm-up starts there): volume_ratio,
+ * price_change_abs, the forward-filled rolling(60, min_periods=20) quantile of
+ * price_change_abs (:376-378, 398), body_size_pct, the rolling
+ * (cumulative_price_window) sums of price_change clipped below / above at 0
+ * (:408-411), open, close. in_b [BQ_NUM_SPIKE_FRAMES_IN_B] 0 / 1 bytes
+ * [S][ld_b]: accel_spike_flag, accel_spike_short_flag (:423-444), upward,
+ * downward (:522-531). aligned != 0: column j of an input row holds candle
+ * first + j (frame-aligned rows); 0: candle j. Outputs are always indexed by
+ * candle.
+ *
+ * Per frame: theta = (volume_cluster_min_ratio, price_break_base_threshold) =
+ * auto_calibrate on rows first .. t (numpy's 'linear' quantile with its
+ * two-sided lerp, NaN dropped, +-inf kept: bq_row_quantile's arithmetic, bit
+ * for bit; the calibration is skipped, leaving params' two defaults, while
+ * either column has no observation), then the flags and labels of row t under
+ * theta, and apply_cooldown's verdict on row t among the labels of rows
+ * first .. t formed under the same theta (post_spike_cooldown_bars <= 0: label
+ * = label_pre). Comparisons only beyond the quantiles: given the inputs, the
+ * bytes equal the method's and the thresholds equal numpy's bits.
+ *
+ * out_b [BQ_NUM_SPIKE_FRAMES_OUT] bytes [S][ld_out] (enum bq_spike_frames_out;
+ * NULL table or entry = skip), vcmr / pbbt fp64 [S][ld_out] (NULL = skip):
+ * latest_signal()'s fields and the instance's thresholds after the call;
+ * 0 / NaN outside the formed candles. workspace: bq_spike_frames_workspace(S,
+ * T) bytes of device memory, 8-byte aligned, private to the call until the
+ * stream has run it. params NULL: the class attributes
+ * (bq_spike_frames_default_params). BQ_EINVAL unless T <=
+ * BQ_SPIKE_FRAMES_MAX_T (a frame's sorted prefix lives in LDS), 1 <=
+ * volume_cluster_window <= BQ_SPIKE_FRAMES_MAX_WINDOW, 2 <=
+ * cumulative_price_window <= BQ_SPIKE_FRAMES_MAX_WINDOW, label_mode in 0..2
+ * (last, first, all), post_spike_cooldown_bars < BQ_SPIKE_FRAMES_MAX_COOLDOWN,
+ * the quantiles lie in [0, 1], the other parameters are finite and every ld >=
+ * T; checked before any launch. S == 0 or T == 0: BQ_OK. Two launches, nothing
+ * allocated.
+ */
+#define BQ_SPIKE_FRAMES_MAX_T 2048
+#define BQ_SPIKE_FRAMES_MAX_WINDOW 30
+#define BQ_SPIKE_FRAMES_MAX_COOLDOWN 64
+typedef struct bq_spike_frames_params {
+  int32_t volume_cluster_window, volume_cluster_min_count, cumulative_price_window, label_mode;
+  int32_t require_both_patterns, require_bullish_spike, post_spike_cooldown_bars, reserved;
+  double cumulative_price_threshold, body_size_pct_min;
+  double volume_cluster_min_ratio, price_break_base_threshold;   /* the instance's values before auto_calibrate */
+  double volume_quantile, price_base_floor_quantile, min_volume_ratio, min_price_abs_floor;
+} bq_spike_frames_params;
+enum bq_spike_frames_in {
+  BQ_SF_VOLUME_RATIO = 0, BQ_SF_PRICE_CHANGE_ABS, BQ_SF_DYN_THRESHOLD, BQ_SF_BODY_SIZE_PCT, BQ_SF_CUM_POS,
+  BQ_SF_CUM_NEG, BQ_SF_OPEN, BQ_SF_CLOSE, BQ_NUM_SPIKE_FRAMES_IN
+};
+enum bq_spike_frames_in_b {
+  BQ_SF_IN_ACCEL = 0, BQ_SF_IN_ACCEL_SHORT, BQ_SF_IN_UPWARD, BQ_SF_IN_DOWNWARD, BQ_NUM_SPIKE_FRAMES_IN_B
+};
+enum bq_spike_frames_out {
+  BQ_SF_LABEL = 0, BQ_SF_LABEL_PRE, BQ_SF_LABEL_SHORT, BQ_SF_LABEL_SHORT_PRE, BQ_SF_VOLUME_CLUSTER_FLAG,
+  BQ_SF_PRICE_BREAK_FLAG, BQ_SF_CUM_BREAK_FLAG, BQ_SF_CUM_BREAK_SHORT_FLAG, BQ_SF_ACCEL_FLAG,
+  BQ_SF_ACCEL_SHORT_FLAG, BQ_SF_UPWARD, BQ_SF_DOWNWARD, BQ_NUM_SPIKE_FRAMES_OUT
+};
+void bq_spike_frames_default_params(bq_spike_frames_params* p);
+size_t bq_spike_frames_workspace(int64_t S, int64_t T);
+int bq_spike_frames(const double* const* in, int64_t ld_in, const uint8_t* const* in_b, int64_t ld_b, int32_t aligned,
+                    const int64_t* lens, const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
+                    const bq_spike_frames_params* params, void* workspace, size_t workspace_bytes, double* vcmr,
+                    double* pbbt, uint8_t* const* out_b, int64_t ld_out, void* stream);
 
 /*
  * PriceTracker.signal() replayed over a panel of 5m frames

@@ -25,6 +25,7 @@ for S, T in ((8, 600), (1000, 400), (12_500, 2_000)):
     strategies.activity_burst_features(o, h, l, c, v, None)
     strategies.pump_score_features(o, h, l, c, v, c[0])
     strategies.failed_spike_features(o, h, l, c, v, qv)
+    strategies.failed_spike_frames(o, h, l, c, v, qv)   # T <= engine.SPIKE_FRAMES_MAX_T at all three shapes
     signals.wilder_rsi(c)
     signals.adx(h, l, c)
     signals.zscore(c)

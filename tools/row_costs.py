@@ -79,6 +79,8 @@ rows = {
     "activity_burst": lambda: strategies.activity_burst_features(o, h, l, c, v, qv),
     "pump_score": lambda: strategies.pump_score_features(o, h, l, c, v, btc),
     "failed_spike": lambda: strategies.failed_spike_features(o, h, l, c, v, qv),
+    # FailedSpikeFade.latest_signal() at every candle: the column stage and bq_spike_frames (T <= 2048)
+    "failed_spike_frames": lambda: strategies.failed_spike_frames(o, h, l, c, v, qv),
     "wilder_rsi": lambda: signals.wilder_rsi(c),
     "adx": lambda: signals.adx(h, l, c),
     "zscore": lambda: signals.zscore(c),
