@@ -388,6 +388,31 @@ RSR_VALUES = ("volume_floor",)
 RSR_MAX_WINDOW = 192
 
 
+class BqGridLadderParams(ctypes.Structure):
+    """Mirror of ``bq_grid_ladder_params`` (include/binquant_amd.h)."""
+
+    _fields_ = [("n", ctypes.c_int32), ("reserved", ctypes.c_int32), ("max_change_pct", ctypes.c_double),
+                ("min_width_pct", ctypes.c_double), ("max_width_pct", ctypes.c_double),
+                ("min_buffer_pct", ctypes.c_double), ("max_buffer_pct", ctypes.c_double),
+                ("atr_multiplier", ctypes.c_double), ("min_long_score", ctypes.c_double)]
+
+
+# bq_grid_ladder_replay: status codes (BQ_GL_*, the index is the code: the points where LadderDeployer.signal()
+# returns, in its order, by the fixed part of its "grid_ladder skipped: ..." log line; "emit" and "no_frame" are this
+# library's), the value columns' order, the context rows' order of signals.grid_ladder_entry (market_regime: an index
+# into MARKET_REGIMES, negative for None; micro_regime / micro_transition: MR_NONE for None) and the tile width
+(BQ_GL_EMIT, BQ_GL_NO_FRAME, BQ_GL_POLICY, BQ_GL_NO_CONTEXT, BQ_GL_NOT_RANGE, BQ_GL_MICRO_REGIME,
+ BQ_GL_SYMBOL_TRANSITION, BQ_GL_BELOW_EMAS, BQ_GL_RS_NOT_POSITIVE, BQ_GL_LONG_SCORE_LOW, BQ_GL_BB_EXPANDING,
+ BQ_GL_PRICE_OUTSIDE, BQ_GL_RANGE_WIDTH) = range(13)
+GL_REASONS = ("emit", "no_frame", "grid_only_policy", "market_context_unavailable", "market_regime_not_range",
+              "symbol_micro_regime", "symbol_transition", "symbol_below_ema20_and_ema50",
+              "relative_strength_vs_btc_not_positive", "long_regime_score_too_low", "bb_width_expanding",
+              "price_outside_range", "range_width")
+GL_VALUES = ("bb_change_pct", "range_width_pct", "breakout_buffer_pct", "breakout_low", "breakout_high")
+GL_CTX_ROWS = ("market_regime", "long_regime_score")
+GRID_LADDER_TILE = 1024
+
+
 class BqTopGainerParams(ctypes.Structure):
     """Mirror of ``bq_top_gainer_params`` (include/binquant_amd.h)."""
 
@@ -485,6 +510,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_impulse_rider": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _P, _P, _I64,
                                         ctypes.POINTER(BqImpulseParams), _P, _PP, _I64, _P]),
     "bq_bb_stable": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, ctypes.c_double, _P, _P, _I64, _P]),
+    "bq_grid_ladder_default_params": (None, [ctypes.POINTER(BqGridLadderParams)]),
+    "bq_grid_ladder_replay": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _I64,
+                                             _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _I64,
+                                             ctypes.POINTER(BqGridLadderParams), _P, _PP, _I64, _P]),
     "bq_top_gainer_default_params": (None, [ctypes.POINTER(BqTopGainerParams)]),
     "bq_top_gainer_entry": (ctypes.c_int, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64,
                                            ctypes.POINTER(BqTopGainerParams), _P, _P, _P, _P, _PP, _I64, _P]),

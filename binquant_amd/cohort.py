@@ -16,8 +16,9 @@ all S symbols of the cohort in one call:
   strategies' decisions (price_tracker, burst_entry below);
 * 15m frame: indicators_enrichment (:415), the 1h resample (:403-407, a9),
   dynamic_btc_beta_corr (:424, a11: index-aligned frames) and the BTC
-  pct_change(96) (:425-428, a12), and on request BuyTheDip's and
-  RelativeStrengthReversalRange's decisions (buy_the_dip, rs_reversal below);
+  pct_change(96) (:425-428, a12), and on request BuyTheDip's,
+  RelativeStrengthReversalRange's and LadderDeployer's decisions (buy_the_dip,
+  rs_reversal, grid_ladder below);
 * the context refresh at the cohort's close: the breadth partials of every
   timestamp and the last timestamp's symbol features
   (live_market_context_accumulator.py:95-297, bq_context_partials);
@@ -78,7 +79,8 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
                    price_tracker_ctx: tuple | None = None, price_tracker_rs: torch.Tensor | None = None,
                    burst_entry: bool = False, burst_route: torch.Tensor | None = None,
                    buy_the_dip: bool = False, ct15: torch.Tensor | None = None,
-                   dip_regimes: tuple | None = None, rs_reversal: tuple | None = None) -> dict[str, torch.Tensor]:
+                   dip_regimes: tuple | None = None, rs_reversal: tuple | None = None,
+                   grid_ladder: tuple | None = None) -> dict[str, torch.Tensor]:
     """Device outputs of process_data for a cohort: 5m / 15m panels [S, T5] /
     [S, T15] float64, ts15 [S, T15] int64 open times, btc_ts15 / btc_c15 [T15]
     (index-aligned with the 15m panel). exact=True runs the strategy
@@ -157,8 +159,16 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
     between replays (context_ok / features_ok may be None): adds, after the
     15m frame and on its stream, RelativeStrengthReversalRange.signal()'s
     decision for the newest 15m candle on v15: rsr.status (uint8) /
-    rsr.volume_floor [S]. Without these keywords the outputs and launches are
-    unchanged. Returns a flat dict of tensors (names prefixed by the stage)."""
+    rsr.volume_floor [S]. grid_ladder: (ctx, ctx_ok, policy_ok, sym) of
+    signals.grid_ladder_entry (ctx float64 [2, 1]; ctx_ok / policy_ok bool /
+    uint8 [1] or None; sym a {signals.GL_SYM_KEYS: [S] tensor} dictionary or
+    None), device tensors the caller updates in place between replays: adds,
+    after the 15m frame and on its stream, LadderDeployer.signal()'s decision
+    for the newest 15m candle on c15 and e15.bb_* (the bands unrounded):
+    gridladder.status (uint8) and gridladder.<name> for signals.GL_VALUES [S].
+    Without these keywords the outputs and launches are unchanged (gates=True's
+    ladder.* included). Returns a flat dict of tensors (names prefixed by the
+    stage)."""
     S, T15 = c15.shape
     B1 = T15 // 4 + 2 if h1_max_bins is None else int(h1_max_bins)
     btc_c = btc_c15.reshape(-1)
@@ -233,6 +243,13 @@ def process_cohort(o5, h5, l5, c5, v5, o15, h15, l15, c15, v15, ts15, btc_ts15, 
             newest = torch.full((S,), T15 - 1, dtype=torch.int64, device=c15.device)
             rsr = signals.rs_reversal_entry(v15, cok, mkt, avg, fok, rs, from_t=newest)
             out["rsr.status"], out["rsr.volume_floor"] = rsr["status"][:, -1], rsr["volume_floor"][:, -1]
+        if grid_ladder is not None:   # LadderDeployer.signal() (:68-151) on the cohort's message: the newest candle only
+            ctx, ctx_ok, policy_ok, sym = grid_ladder
+            newest = torch.full((S,), T15 - 1, dtype=torch.int64, device=c15.device)
+            gl = signals.grid_ladder_entry(c15, out["e15.bb_upper"], out["e15.bb_mid"], out["e15.bb_lower"], ctx,
+                                           ctx_ok, policy_ok, sym=sym, from_t=newest)
+            for k in ("status",) + signals.GL_VALUES:
+                out[f"gridladder.{k}"] = gl[k][:, -1]
 
     def context(out):   # klines_provider.py:181-199
         part, last = engine.context_partials(h15, l15, c15, max_bars=max_bars, last=True)

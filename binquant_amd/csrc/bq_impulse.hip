@@ -29,7 +29,9 @@
 //   mid > 0, and |w[t] - w[t-n+1]| / w[t-n+1] * 100 <= max_change_pct. The
 //   widths and a bad-row bitmask (a wave ballot per 64 candles) of the tile
 //   and the 64 candles before it go to LDS; "all n rows valid" is a popcount
-//   of the window's mask bits, not a walk.
+//   of the window's mask bits, not a walk (bq_bbwalk.h, shared with
+//   bq_ladder.hip).
+#include "bq_bbwalk.h"
 #include "bq_bench_lookup.h"
 #include "bq_device.h"
 #include "binquant_amd.h"
@@ -190,14 +192,8 @@ __global__ __launch_bounds__(BS_NT) void bb_stable_kernel(const StableArgs A) {
   // width <= 0 (:49-53; a NaN row passes both tests). Slots outside the row
   // are read only by candles that return before the walk (len(df) < n).
   for (int i = tid; i < BS_H + BS_TILE; i += BS_NT) {
-    const int t = t0 - BS_H + i;
-    double w = qnan();
-    bool bad = false;
-    if (t >= 0 && t < T) {
-      const double m = md[t];
-      w = (up[t] - lw[t]) / m;
-      bad = m <= 0.0 || w <= 0.0;
-    }
+    double w;
+    const bool bad = bb_slot(up, md, lw, t0 - BS_H + i, T, w);
     sW[i] = w;
     const uint64_t bm = __ballot(bad);   // slots i - lane .. i - lane + 63 (BS_NT % 64 == 0)
     if ((tid & (WAVE - 1)) == 0) sBad[i / WAVE] = bm;
@@ -211,16 +207,11 @@ __global__ __launch_bounds__(BS_NT) void bb_stable_kernel(const StableArgs A) {
   for (int q = 0; q < BS_CPT; ++q) {
     const int u = q * BS_NT + tid, t = t0 + u;
     if (t >= T) continue;
-    const int k = BS_H + u, lo = k - (n - 1);   // the window's slots lo .. k (lo >= 1)
-    // bad rows among the last n (at most two mask words)
-    const int wl = lo / WAVE, wh = k / WAVE;
-    const uint64_t hi_mask = ~0ull >> (WAVE - 1 - (k & (WAVE - 1)));   // bits 0 .. k % 64
-    const uint64_t lo_mask = ~0ull << (lo & (WAVE - 1));                // bits lo % 64 .. 63
-    const int nbad = wl == wh ? __popcll(sBad[wh] & hi_mask & lo_mask)
-                              : __popcll(sBad[wl] & lo_mask) + __popcll(sBad[wh] & hi_mask);
+    const int k = BS_H + u;   // the window's slots k - (n - 1) .. k (>= 1)
+    const BbWindow win = bb_window(k, n);
+    const int nbad = BQ_BB_WINDOW_BAD(sBad, win);
     const bool reached = t < len && t + 1 - first >= n && nbad == 0;   // change_pct is computed (:55)
-    const double w0 = sW[lo], w1 = sW[k];
-    const double change = fabs((w1 - w0) / w0) * 100.0;
+    const double change = bb_change(sW[win.lo], sW[k]);
     const int64_t o = s * A.ld_out + t;
     A.stable[o] = reached && change <= A.max_change ? 1 : 0;
     if (A.change) A.change[o] = reached ? change : qnan();

@@ -1414,8 +1414,8 @@ def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
     return cols, ld
 
 
-# ---- the argument layer of the eight replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
-# range_fade, buy_the_dip, bb_extreme, rs_reversal): each check raises the text the wrappers raised themselves, with the entry's name substituted
+# ---- the argument layer of the nine replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
+# range_fade, buy_the_dip, bb_extreme, rs_reversal, grid_ladder): each check raises the text the wrappers raised themselves, with the entry's name substituted
 
 def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None) -> dict:
     """defaults overlaid with params; int_keys given: every other parameter is a finite float."""
@@ -2450,6 +2450,89 @@ def rs_reversal_replay(volume: torch.Tensor, context_ok: torch.Tensor | None, ma
         _ptr(vv), _row_stride(vv), _ptr(cok), _ptr(mk), _ptr(ar), Tc, _ptr(fok), _ptr(rsv), ld_sym, _ptr(lens),
         _ptr(first_t), _ptr(from_t), S, T, ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
     _lib.check(st, "bq_rs_reversal_replay")
+    return status, outs
+
+
+GRID_LADDER_TILE = _lib.GRID_LADDER_TILE   # candles per workgroup tile of bq_grid_ladder_replay
+GRID_LADDER_DEFAULTS = dict(   # LadderDeployer's class attributes (strategies/grid/ladder_deployer.py:16-28)
+    n=8, max_change_pct=20.0, min_width_pct=1.5, max_width_pct=8.0, min_buffer_pct=0.5, max_buffer_pct=4.0,
+    atr_multiplier=1.5, min_long_score=0.2)
+_GL_INT_PARAMS = ("n",)
+_GL_FLAGS = (torch.uint8, torch.bool)
+_GL_SYM = (("ok", _GL_FLAGS), ("micro_regime", (torch.uint8,)), ("micro_transition", (torch.uint8,)),
+           ("above_ema20", _GL_FLAGS), ("above_ema50", _GL_FLAGS), ("rs_vs_btc", (torch.float64,)),
+           ("atr_pct", (torch.float64,)))
+
+
+@device_entry
+def grid_ladder_replay(c: torch.Tensor, bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tensor,
+                       market_regime: torch.Tensor, long_regime_score: torch.Tensor,
+                       ctx_ok: torch.Tensor | None = None, policy_ok: torch.Tensor | None = None, *, bands=None,
+                       sym=None, first_t=None, lens=None, from_t=None, columns=_lib.GL_VALUES, **params):
+    """LadderDeployer.signal() replayed over the panel
+    (strategies/grid/ladder_deployer.py:58-187; bq_grid_ladder_replay): column
+    t of row s = the method on the message whose frame is
+    df_15m.iloc[first_t[s]:t + 1] with current_price = close[t]; candles
+    max(from_t[s], first_t[s]) .. lens[s] - 1 are replayed. ENABLED and the
+    futures check are the caller's; the method keeps no state. c and the
+    frame's bb_upper / bb_mid / bb_lower (what _bb_stable iterates over) [S, T]
+    float64 with unit stride along T and any row pitch. bands: None (the
+    frame's columns are what signal() receives; each is read once) or the
+    (bb_high, bb_mid, bb_low) [S, T] float64 tensors as the caller rounded
+    them. Per candle time, on the device, [1] (one message) or [T]:
+    market_regime int8 (_lib.MARKET_REGIMES codes, negative: None),
+    long_regime_score float64, ctx_ok bool / uint8 (False: latest_market_context
+    is None; None: present), policy_ok bool / uint8
+    (grid_only_policy.allow_grid_ladder; None: allowed). sym: None (no symbol
+    has features in the snapshot) or the (ok uint8 / bool, micro_regime uint8,
+    micro_transition uint8, above_ema20, above_ema50 uint8 / bool, rs_vs_btc
+    float64, atr_pct float64) tensors, all [S] or all [S, T]; the codes index
+    _lib.MICRO_REGIMES / _lib.MICRO_TRANSITIONS, _lib.MR_NONE for None. Returns
+    (status uint8 [S, T] (_lib.GL_REASONS' indices), {name: float64 [S, T]}
+    for `columns`, a subset of _lib.GL_VALUES, NaN where the method did not
+    compute them). Nothing is read back and every allocation is by shape: the
+    call can be captured. params: GRID_LADDER_DEFAULTS' keys."""
+    par = _replay_params("grid_ladder_replay", GRID_LADDER_DEFAULTS, params, _GL_INT_PARAMS)
+    if not 1 <= int(par["n"]) <= _lib.BB_STABLE_MAX_N:
+        raise ValueError(f"grid_ladder_replay: n in 1..{_lib.BB_STABLE_MAX_N}")
+    columns = tuple(columns)
+    _replay_columns("grid_ladder_replay", columns, _lib.GL_VALUES)
+    S, T = _replay_shape(c)
+    bb = [(bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower")]
+    if bands is not None and len(bands) != 3:
+        raise ValueError("bands: expected (bb_high, bb_mid, bb_low)")
+    bd = list(zip(bands, ("bb_high", "bb_mid_arg", "bb_low"))) if bands is not None else []
+    _replay_panels([(c, "close")] + bb + bd, S, T)
+    mk = _replay_regime(market_regime, "market_regime", ((1,), (T,)))
+    if mk is None:
+        raise ValueError("market_regime: expected an int8 tensor of shape (1,) or (T,) (negative codes: None)")
+    Tc = int(mk.numel())
+    if (not isinstance(long_regime_score, torch.Tensor) or long_regime_score.dtype != torch.float64
+            or tuple(long_regime_score.shape) != (Tc,)):
+        raise ValueError(f"long_regime_score: expected a float64 tensor of shape {(Tc,)}")
+    for x, name in ((ctx_ok, "ctx_ok"), (policy_ok, "policy_ok")):
+        if x is not None and (not isinstance(x, torch.Tensor) or x.dtype not in _GL_FLAGS or tuple(x.shape) != (Tc,)):
+            raise ValueError(f"{name}: expected a bool / uint8 tensor of shape {(Tc,)}")
+    sy, ld_sym = _replay_sym(sym, _GL_SYM, S, T)
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
+    cc = _check_panel(c, "close")
+    bbs, ld_bb = _common_pitch([_check_panel(x, n) for x, n in bb])
+    bds, ld_bd = _common_pitch([_check_panel(x, n) for x, n in bd]) if bd else ([None] * 3, ld_bb)
+    _replay_on_device("market_regime / long_regime_score / ctx_ok / policy_ok / sym",
+                      [mk, long_regime_score, ctx_ok, policy_ok, *sy])
+    mk, sc = mk.contiguous(), long_regime_score.contiguous()
+    cok = ctx_ok.contiguous() if ctx_ok is not None else None
+    pok = policy_ok.contiguous() if policy_ok is not None else None
+    dev = c.device
+    lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
+    p = _replay_struct(_lib.BqGridLadderParams, par, _GL_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.GL_VALUES, S, T, dev)
+    st = _lib.load().bq_grid_ladder_replay(
+        _ptr(cc), _row_stride(cc), _ptr(bbs[0]), _ptr(bbs[1]), _ptr(bbs[2]), ld_bb, _ptr(bds[0]), _ptr(bds[1]),
+        _ptr(bds[2]), ld_bd, _ptr(pok), _ptr(cok), _ptr(mk), _ptr(sc), Tc, _ptr(sy[0]), _ptr(sy[1]), _ptr(sy[2]),
+        _ptr(sy[3]), _ptr(sy[4]), _ptr(sy[5]), _ptr(sy[6]), ld_sym, _ptr(lens), _ptr(first_t), _ptr(from_t), S, T,
+        ctypes.byref(p), _ptr(status), vals, T, _stream_handle(None))
+    _lib.check(st, "bq_grid_ladder_replay")
     return status, outs
 
 

@@ -71,6 +71,14 @@ prefix frame df.iloc[:t + 1]:
                      the 24 h volume floor (Series.quantile, sorted only
                      where a candle passes the route), one pass
                      (bq_rsreversal.hip)
+* grid_ladder_entry  the decisions of LadderDeployer.signal()
+                     (strategies/grid/ladder_deployer.py:58-187) on the 15m
+                     frame: the policy, context and symbol gates, _bb_stable,
+                     the price and width tests, and the deployment's
+                     range_width_pct, breakout buffer and breakout_low / high,
+                     one pass (bq_ladder.hip), with grid_only_policy for
+                     GridOnlyPolicy.resolve (market_regime/grid_only_policy.py
+                     :121-158)
 
 wilder_rsi, zscore and adx default to the time-parallel kernels of
 bq_signals.hip (one launch each, 1e-9 of pandas); exact=True runs the
@@ -1381,3 +1389,109 @@ def rs_reversal_entry(volume, context_ok, market_regime, average_return, feature
     status, vals = engine.rs_reversal_replay(volume, context_ok, market_regime, average_return, features_ok, rs,
                                              first_t=first_t, lens=lens, from_t=from_t, columns=columns, **params)
     return {"status": status, **vals}
+
+
+# ---- the 15m grid ladder: LadderDeployer ----------------------------------------------------------------------------
+# bq_grid_ladder_replay's status codes: where LadderDeployer.signal() returned, in the method's order (GL_REASONS:
+# its "grid_ladder skipped: ..." log lines by their fixed part; "emit" and "no_frame" are this library's names)
+(GL_EMIT, GL_NO_FRAME, GL_POLICY, GL_NO_CONTEXT, GL_NOT_RANGE, GL_MICRO_REGIME, GL_SYMBOL_TRANSITION, GL_BELOW_EMAS,
+ GL_RS_NOT_POSITIVE, GL_LONG_SCORE_LOW, GL_BB_EXPANDING, GL_PRICE_OUTSIDE, GL_RANGE_WIDTH) = range(13)
+GL_REASONS = dict(enumerate(_lib.GL_REASONS))
+GL_VALUES = _lib.GL_VALUES
+GL_CTX_ROWS = _lib.GL_CTX_ROWS
+GL_SYM_KEYS = ("ok", "micro_regime", "micro_transition", "above_ema20", "above_ema50", "rs_vs_btc", "atr_pct")
+GL_BLOCKING_TRANSITIONS = ("BREAKDOWN", "VOLATILITY_EXPANSION", "ENTERED_TREND_DOWN")
+
+
+def grid_ladder_entry(c, bb_upper, bb_mid, bb_lower, ctx, ctx_ok=None, policy_ok=None, *, bands=None, sym=None,
+                      first_t=None, lens=None, from_t=None, columns=GL_VALUES, **params):
+    """The decisions of LadderDeployer.signal() (strategies/grid/ladder_deployer.py
+    :58-187) and the numbers its deployment is built from, for every candle
+    of a 15m panel in one pass (engine.grid_ladder_replay,
+    bq_grid_ladder_replay). Column t of row s = the method on the message
+    whose frame is df_15m.iloc[first_t[s]:t + 1] with current_price =
+    close[t]; candles from_t[s] .. lens[s] - 1 are replayed. The method keeps
+    no state; ENABLED and the market_type != FUTURES return (:61-67) are the
+    caller's. c and the frame's bb_upper / bb_mid / bb_lower (the columns
+    _bb_stable iterates over) [S, T] float64. bands: None (the frame's own
+    columns are what signal() receives; each is read once) or the (bb_high,
+    bb_mid, bb_low) [S, T] float64 the caller formed, e.g. the evaluator's
+    round_numbers(.., 6) of bb_spreads: the rounding is the caller's step. ctx
+    [2, 1] (one message) or [2, T] float64 (GL_CTX_ROWS: market_regime, an
+    index into _lib.MARKET_REGIMES, negative for None, and long_regime_score),
+    ctx_ok [1] / [T] (False: latest_market_context is None; None: present) and
+    policy_ok [1] / [T] (grid_only_policy.allow_grid_ladder, e.g.
+    grid_only_policy's first result; None: allowed), all on the device. sym:
+    None (no symbol has features in the snapshot) or {GL_SYM_KEYS: tensor},
+    all [S] or all [S, T]: ok (False: resolve_symbol_features gave None),
+    micro_regime / micro_transition as uint8 indices into _lib.MICRO_REGIMES /
+    _lib.MICRO_TRANSITIONS (_lib.MR_NONE: None), above_ema20 / above_ema50,
+    rs_vs_btc, atr_pct. params: engine.GRID_LADDER_DEFAULTS' keys.
+
+    Returns {"status": uint8 [S, T] (GL_* codes, GL_REASONS their names; 0 =
+    the deployment goes out), and the `columns` of GL_VALUES, float64 [S, T],
+    NaN where the method did not compute them}: bb_change_pct where it reached
+    _bb_stable and the walk got to its last line, range_width_pct on
+    GL_RANGE_WIDTH and GL_EMIT, breakout_buffer_pct (indicators'
+    atr_buffer_pct), breakout_low and breakout_high on GL_EMIT; range_low /
+    range_high are the bands passed. autotrade_settings, model_dump,
+    datetime.now, GridDeploymentRequest and the dispatch order stay host
+    steps."""
+    if (not isinstance(ctx, torch.Tensor) or ctx.dtype != torch.float64 or ctx.dim() != 2
+            or ctx.shape[0] != len(GL_CTX_ROWS)):
+        raise ValueError(f"ctx: expected a float64 tensor of shape {(len(GL_CTX_ROWS), 1)} or "
+                         f"{(len(GL_CTX_ROWS), 'T')} (rows {GL_CTX_ROWS})")
+    status, vals = engine.grid_ladder_replay(
+        c, bb_upper, bb_mid, bb_lower, ctx[0].to(torch.int8), ctx[1], ctx_ok, policy_ok, bands=bands,
+        sym=_pick(sym, GL_SYM_KEYS, "sym"), first_t=first_t, lens=lens, from_t=from_t, columns=columns, **params)
+    return {"status": status, **vals}
+
+
+# GridOnlyPolicy.resolve's reasons (market_regime/grid_only_policy.py:121-158) as uint8 codes, in the method's order;
+# the f-string family is expanded over the regimes outside GRID_ONLY_REGIMES. An active policy's reason carries the
+# breadth source the host chose ("breadth_momentum_<direction>_<source>"): the code names its fixed part
+GRID_ONLY_REGIMES = ("RANGE", "TRANSITIONAL")
+GRID_POLICY_REASONS = (("market_context_unavailable", "market_regime_unavailable")
+                       + tuple(f"market_regime_{r.lower()}" for r in _lib.MARKET_REGIMES if r not in GRID_ONLY_REGIMES)
+                       + ("breadth_momentum_unavailable", "breadth_momentum_toward_trend",
+                          "breadth_momentum_toward_range", "breadth_momentum_flat"))
+
+
+def grid_only_policy(context_ok, market_regime, previous, latest):
+    """GridOnlyPolicy.resolve (market_regime/grid_only_policy.py:121-158) after
+    _breadth_pair, per candle time: context_ok bool [T] (False: the context is
+    None), market_regime int8 [T] (_lib.MARKET_REGIMES codes, negative: None),
+    previous / latest float64 [T]: the pair _breadth_pair returned (either
+    NaN: it returned None). Choosing the breadth source, dropping its
+    non-finite values and ordering it by timestamp (:67-119) read a
+    server-side series and stay on the host. Returns (allow bool,
+    reason uint8 (GRID_POLICY_REASONS' index), momentum_points float64 —
+    (latest - previous) * 100 where the policy is active, NaN elsewhere), each
+    of market_regime's shape. allow is grid_ladder_entry's policy_ok. One
+    fused element-wise program."""
+    shape = tuple(market_regime.shape)
+    T = int(market_regime.numel())
+    R = GRID_POLICY_REASONS.index
+    mk = _lib.MARKET_REGIMES.index
+    CTX = F.inp(context_ok.to(torch.bool).reshape(-1))
+    MKT = F.inp(market_regime.to(torch.float64).reshape(-1))
+    PREV, LAT = F.inp(previous.reshape(-1)), F.inp(latest.reshape(-1))
+    grid_regime = (MKT == float(mk(GRID_ONLY_REGIMES[0]))) | (MKT == float(mk(GRID_ONLY_REGIMES[1])))
+    no_pair = F.isnan(PREV) | F.isnan(LAT)
+    la, pa = LAT.abs(), PREV.abs()
+    outside = [r for r in _lib.MARKET_REGIMES if r not in GRID_ONLY_REGIMES]
+    family = F.const(float(R("market_regime_" + outside[0].lower())))   # market_regime_<name>, by the regime's code
+    for r in outside[1:]:
+        family = F.where(MKT == float(mk(r)), float(R("market_regime_" + r.lower())), family)
+    code = _first_code([
+        (~CTX, R("market_context_unavailable")),
+        (MKT < 0.0, R("market_regime_unavailable")),
+        (~grid_regime, family),
+        (no_pair, R("breadth_momentum_unavailable")),
+        (la > pa, R("breadth_momentum_toward_trend")),
+        (la < pa, R("breadth_momentum_toward_range")),
+    ], R("breadth_momentum_flat"))
+    allow = CTX & grid_regime & ~no_pair & ((la > pa) | (la < pa))
+    res = F.run({"reason": code, "allow": allow, "momentum_points": F.where(allow, (LAT - PREV) * 100.0, NAN)}, 1, T)
+    return (res["allow"].reshape(shape), res["reason"].to(torch.uint8).reshape(shape),
+            res["momentum_points"].reshape(shape))

@@ -49,6 +49,9 @@
  *                         (strategies/relative_strength_impulse_rider.py:69-198)
  *   bq_bb_stable       <- LadderDeployer._bb_stable
  *                         (strategies/grid/ladder_deployer.py:42-56)
+ *   bq_grid_ladder_replay <- LadderDeployer.signal(): the policy, context and symbol
+ *                         gates, _bb_stable, the price and width tests and the
+ *                         deployment's range plan (strategies/grid/ladder_deployer.py:58-187)
  *   bq_retest_replay   <- GradualGainerRetest.signal()'s watchlist state machine
  *                         (strategies/gradual_gainer_retest.py:222-308)
  *   bq_spike_fade_replay <- FailedSpikeFade.signal()'s pending-spike state machine
@@ -1220,6 +1223,102 @@ int bq_impulse_rider(const double* open, const double* high, const double* low, 
 int bq_bb_stable(const double* bb_upper, const double* bb_mid, const double* bb_lower, int64_t ld_in,
                  const int64_t* lens, const int64_t* first_t, int64_t S, int64_t T, int32_t n,
                  double max_change_pct, uint8_t* stable, double* change_pct, int64_t ld_out, void* stream);
+
+/*
+ * LadderDeployer.signal(current_price, bb_high, bb_mid, bb_low) replayed over
+ * a [S][T] panel of 15m frames (strategies/grid/ladder_deployer.py:58-187):
+ * column t of row s is the method on the message whose frame is
+ * df_15m.iloc[first:t + 1], first = first_t[s] (NULL: 0); candles
+ * max(from_t[s], first) .. lens[s] - 1 are replayed (NULL: 0 / T). ENABLED and
+ * the market_type != FUTURES return (:61-67) are the caller's; the method
+ * keeps no state. One launch, nothing allocated, nothing read back.
+ *
+ * close [S][ld_c] is current_price. bb_upper / bb_mid / bb_lower [S][ld_bb]
+ * are the frame's columns, which _bb_stable iterates over. bb_high /
+ * bb_mid_arg / bb_low [S][ld_bands] are the bands as passed to signal() (the
+ * evaluator rounds them); all three NULL, or equal to the frame's pointers
+ * and pitch: the frame's columns are what signal() receives, and each is read
+ * once. Per candle time, each of length ctx_T, 1 (one message) or T:
+ * policy_ok (grid_only_policy.allow_grid_ladder; NULL: allowed), ctx_ok (0:
+ * latest_market_context is None; NULL: present), market_regime (int8, an
+ * index into "TREND_UP", "TREND_DOWN", "RANGE", "HIGH_STRESS", "TRANSITIONAL";
+ * negative: None) and long_regime_score. The symbol's entry in the snapshot,
+ * [S] with ld_sym 0 or [S][ld_sym] per candle: sym_ok (0:
+ * resolve_symbol_features gave None; NULL: no symbol has features),
+ * sym_micro_regime / sym_micro_transition (indices into the micro_regime /
+ * micro_regime_transition literals, BQ_MR_NONE for None), sym_above_ema20 /
+ * sym_above_ema50, sym_rs_vs_btc and sym_atr_pct.
+ *
+ * Per candle, in the method's order (the first match wins):
+ *    # condition                                              status             lines
+ *    1 t outside [max(from_t, first), lens)                   NO_FRAME
+ *    2 policy_ok false                                        POLICY             :70-75
+ *    3 ctx_ok false                                           NO_CONTEXT         :76
+ *    4 market_regime != RANGE                                 NOT_RANGE          :79
+ *    5 sym_ok false, or micro_regime != RANGE                 MICRO_REGIME       :83-88
+ *    6 micro_transition is BREAKDOWN, VOLATILITY_EXPANSION    SYMBOL_TRANSITION  :89
+ *      or ENTERED_TREND_DOWN
+ *    7 neither above_ema20 nor above_ema50                    BELOW_EMAS         :92
+ *    8 rs_vs_btc <= 0 (a NaN goes on)                         RS_NOT_POSITIVE    :95
+ *    9 long_regime_score < min_long_score (a NaN goes on)     LONG_SCORE_LOW     :98
+ *   10 not _bb_stable(n, max_change_pct) (bq_bb_stable's      BB_EXPANDING       :101-106
+ *      rules, on the frame's columns)
+ *   11 not (bb_low < close < bb_high) (false on any NaN)      PRICE_OUTSIDE      :109
+ *   12 not (min_width_pct <= range_width_pct <=               RANGE_WIDTH        :115-119
+ *      max_width_pct)
+ *    0 otherwise                                              EMIT
+ * range_width_pct = ((bb_high - bb_low) / bb_mid_arg) * 100 if bb_mid_arg > 0
+ * else 0 (a NaN or non-positive mid: 0). On EMIT, raw = (atr_pct * 100) *
+ * atr_multiplier, breakout_buffer_pct = max(min_buffer_pct, min(max_buffer_pct,
+ * raw)) with Python's min / max (the first argument unless the second compares
+ * strictly beyond it: a NaN atr_pct gives max_buffer_pct), breakout_low =
+ * bb_low * (1 - buffer / 100), breakout_high = bb_high * (1 + buffer / 100);
+ * range_low / range_high are bb_low / bb_high themselves. Every value is the
+ * method's IEEE operations in its order (bit-exact).
+ *
+ * status [S][ld_out] bytes (BQ_GL_*), values: NULL or BQ_GL_NVALUES host
+ * pointers to [S][ld_out] doubles (a NULL entry is skipped) in BQ_GL_V_* order:
+ * bb_change_pct where the method reached _bb_stable and its walk reached :55,
+ * range_width_pct on RANGE_WIDTH and EMIT, breakout_buffer_pct / breakout_low /
+ * breakout_high on EMIT; NaN elsewhere. params NULL:
+ * bq_grid_ladder_default_params. BQ_EINVAL, before any launch, unless every
+ * ld >= T (ld_sym: or 0), ctx_T is 1 or T, 1 <= n <= BQ_BB_STABLE_MAX_N, the
+ * thresholds are finite and S * ceil(T / BQ_GRID_LADDER_TILE) fits a grid.
+ * S == 0 or T == 0: BQ_OK.
+ */
+#define BQ_GRID_LADDER_TILE 1024   /* candles per workgroup tile */
+#define BQ_GL_NVALUES 5
+#define BQ_GL_REGIME_RANGE 2                    /* market_regime / micro_regime "RANGE" */
+#define BQ_GL_TRANSITION_VOLATILITY_EXPANSION 0 /* micro_regime_transition literals */
+#define BQ_GL_TRANSITION_BREAKDOWN 2
+#define BQ_GL_TRANSITION_ENTERED_TREND_DOWN 6
+typedef struct bq_grid_ladder_params {
+  int32_t n;               /* 8    MIN_BB_WIDTH_STABILITY_CANDLES */
+  int32_t reserved;
+  double max_change_pct;   /* 20.0 MAX_BB_WIDTH_CHANGE_PCT */
+  double min_width_pct;    /* 1.5  MIN_RANGE_WIDTH_PCT */
+  double max_width_pct;    /* 8.0  MAX_RANGE_WIDTH_PCT */
+  double min_buffer_pct;   /* 0.5  MIN_BREAKOUT_BUFFER_PCT */
+  double max_buffer_pct;   /* 4.0  MAX_BREAKOUT_BUFFER_PCT */
+  double atr_multiplier;   /* 1.5  BREAKOUT_ATR_MULTIPLIER */
+  double min_long_score;   /* 0.2  MIN_LONG_REGIME_SCORE */
+} bq_grid_ladder_params;
+enum { BQ_GL_EMIT = 0, BQ_GL_NO_FRAME, BQ_GL_POLICY, BQ_GL_NO_CONTEXT, BQ_GL_NOT_RANGE, BQ_GL_MICRO_REGIME,
+       BQ_GL_SYMBOL_TRANSITION, BQ_GL_BELOW_EMAS, BQ_GL_RS_NOT_POSITIVE, BQ_GL_LONG_SCORE_LOW, BQ_GL_BB_EXPANDING,
+       BQ_GL_PRICE_OUTSIDE, BQ_GL_RANGE_WIDTH };
+/* value columns: bb_change_pct, range_width_pct, breakout_buffer_pct, breakout_low, breakout_high */
+enum { BQ_GL_V_BB_CHANGE = 0, BQ_GL_V_RANGE_WIDTH, BQ_GL_V_BUFFER, BQ_GL_V_BREAKOUT_LOW, BQ_GL_V_BREAKOUT_HIGH };
+void bq_grid_ladder_default_params(bq_grid_ladder_params* p);
+int bq_grid_ladder_replay(const double* close, int64_t ld_c, const double* bb_upper, const double* bb_mid,
+                          const double* bb_lower, int64_t ld_bb, const double* bb_high, const double* bb_mid_arg,
+                          const double* bb_low, int64_t ld_bands, const uint8_t* policy_ok, const uint8_t* ctx_ok,
+                          const int8_t* market_regime, const double* long_regime_score, int64_t ctx_T,
+                          const uint8_t* sym_ok, const uint8_t* sym_micro_regime,
+                          const uint8_t* sym_micro_transition, const uint8_t* sym_above_ema20,
+                          const uint8_t* sym_above_ema50, const double* sym_rs_vs_btc, const double* sym_atr_pct,
+                          int64_t ld_sym, const int64_t* lens, const int64_t* first_t, const int64_t* from_t,
+                          int64_t S, int64_t T, const bq_grid_ladder_params* params, uint8_t* status,
+                          double* const* values, int64_t ld_out, void* stream);
 
 /*
  * TopGainerEarlyMomentum at every candle of the panel, one pass over the row

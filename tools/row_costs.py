@@ -107,6 +107,17 @@ rows = {
              "micro_transition": torch.full((S,), 255, dtype=torch.uint8, device="cuda"),
              "atr_pct": torch.full((S,), 0.01, dtype=torch.float64, device="cuda"),
              "bb_width": torch.full((S,), 0.02, dtype=torch.float64, device="cuda")}),
+    # LadderDeployer.signal()'s decisions, every output column (the frame's bands h / c / l as stand-in columns, read
+    # once; one passing RANGE context for every candle, a passing snapshot [S])
+    "grid_ladder_entry": lambda: signals.grid_ladder_entry(
+        c, h, c, l, torch.tensor([[2.0], [0.5]], dtype=torch.float64, device="cuda"),
+        sym={"ok": torch.ones(S, dtype=torch.uint8, device="cuda"),
+             "micro_regime": torch.full((S,), 2, dtype=torch.uint8, device="cuda"),
+             "micro_transition": torch.full((S,), 255, dtype=torch.uint8, device="cuda"),
+             "above_ema20": torch.ones(S, dtype=torch.uint8, device="cuda"),
+             "above_ema50": torch.ones(S, dtype=torch.uint8, device="cuda"),
+             "rs_vs_btc": torch.full((S,), 0.1, dtype=torch.float64, device="cuda"),
+             "atr_pct": torch.full((S,), 0.01, dtype=torch.float64, device="cuda")}),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
