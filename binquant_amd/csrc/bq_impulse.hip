@@ -33,16 +33,14 @@
 //   bq_ladder.hip).
 #include "bq_bbwalk.h"
 #include "bq_bench_lookup.h"
+#include "bq_candletile.h"
 #include "bq_device.h"
 #include "binquant_amd.h"
 
 namespace bq {
 
-constexpr int IR_TILE = BQ_IMPULSE_TILE;   // candles per workgroup tile
-constexpr int IR_NT = 256;                 // threads
-constexpr int IR_CPT = IR_TILE / IR_NT;    // candles per thread
-constexpr int IR_HC = 8;                   // close slots before the tile (the stencil reaches t - 6)
-static_assert(IR_TILE % IR_NT == 0 && IR_NT % WAVE == 0, "whole waves, whole candles per thread");
+constexpr int IR_TILE = CT_TILE, IR_NT = CT_NT, IR_CPT = CT_CPT;   // the kernel's names for the geometry
+constexpr int IR_HC = 8;   // close slots before the tile (the stencil reaches t - 6)
 
 struct ImpulseArgs {
   const double *open, *high, *low, *close, *atr;
@@ -161,12 +159,9 @@ __global__ __launch_bounds__(IR_NT) void impulse_kernel(const ImpulseArgs A) {
 }
 
 // ---- LadderDeployer._bb_stable ------------------------------------------------
-constexpr int BS_TILE = BQ_IMPULSE_TILE;
-constexpr int BS_NT = 256;
-constexpr int BS_CPT = BS_TILE / BS_NT;
+constexpr int BS_TILE = CT_TILE, BS_NT = CT_NT, BS_CPT = CT_CPT;
 constexpr int BS_H = WAVE;   // slots before the tile (n <= 64 reaches t - 63)
-static_assert(BS_TILE % BS_NT == 0 && BS_NT % WAVE == 0 && BS_H % WAVE == 0 && BQ_BB_STABLE_MAX_N <= BS_H,
-              "mask words are whole waves of slots");
+static_assert(BS_H % WAVE == 0 && BQ_BB_STABLE_MAX_N <= BS_H, "mask words are whole waves of slots");
 
 struct StableArgs {
   const double *upper, *mid, *lower;
@@ -243,16 +238,15 @@ extern "C" int bq_impulse_rider(const double* open, const double* high, const do
                                 int64_t ld_out, void* stream) {
   using namespace bq;
   if (!open || !high || !low || !close || !atr || !open_time || !status || S < 0 || T < 0 || ld_in < T ||
-      ld_atr < T || ld_ts < T || ld_out < T || nb < 0 || nb > 0x7fffffff || T > 0x7fffffff - 2 * IR_TILE)
+      ld_atr < T || ld_ts < T || ld_out < T || nb < 0 || nb > 0x7fffffff)
     return BQ_EINVAL;
-  if (nb > 0 && (!bench_ts || !bench_close)) return BQ_EINVAL;
+  int64_t tiles;
+  if (!candle_tiles(S, T, tiles) || (nb > 0 && (!bench_ts || !bench_close))) return BQ_EINVAL;
   ImpulseArgs A;
   if (params) A.p = *params;
   else bq_impulse_default_params(&A.p);
   if (A.p.min_history < 7) return BQ_EINVAL;   // the stencil reaches t - 6
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t tiles = (T + IR_TILE - 1) / IR_TILE;
-  if (tiles * S > 0x7fffffff) return BQ_EINVAL;
   A.open = open;
   A.high = high;
   A.low = low;
@@ -271,7 +265,7 @@ extern "C" int bq_impulse_rider(const double* open, const double* high, const do
   A.nb = (int)nb;
   A.tiles = (int)tiles;
   A.status = status;
-  for (int k = 0; k < BQ_IR_NVALUES; ++k) A.val[k] = values ? values[k] : nullptr;
+  tile_values(A.val, values);
   hipLaunchKernelGGL(impulse_kernel, dim3((unsigned)(tiles * S)), dim3(IR_NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }
@@ -281,12 +275,11 @@ extern "C" int bq_bb_stable(const double* bb_upper, const double* bb_mid, const 
                             double max_change_pct, uint8_t* stable, double* change_pct, int64_t ld_out,
                             void* stream) {
   using namespace bq;
+  int64_t tiles;
   if (!bb_upper || !bb_mid || !bb_lower || !stable || S < 0 || T < 0 || ld_in < T || ld_out < T || n < 1 ||
-      n > BQ_BB_STABLE_MAX_N || T > 0x7fffffff - 2 * BS_TILE)
+      n > BQ_BB_STABLE_MAX_N || !candle_tiles(S, T, tiles))
     return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t tiles = (T + BS_TILE - 1) / BS_TILE;
-  if (tiles * S > 0x7fffffff) return BQ_EINVAL;
   StableArgs A;
   A.upper = bb_upper;
   A.mid = bb_mid;

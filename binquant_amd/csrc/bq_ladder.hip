@@ -27,6 +27,7 @@
 //   time, + 21 B of symbol snapshot where it is per candle) and 1 + 5 x 8 B
 //   out per candle; a NULL value column is skipped (wave-uniform).
 #include "bq_bbwalk.h"
+#include "bq_candletile.h"
 #include "bq_replay.h"
 #include "binquant_amd.h"
 
@@ -34,12 +35,9 @@
 
 namespace bq {
 
-constexpr int GL_TILE = BQ_GRID_LADDER_TILE;   // candles per workgroup tile
-constexpr int GL_NT = 256;                     // threads
-constexpr int GL_CPT = GL_TILE / GL_NT;        // candles per thread
-constexpr int GL_H = WAVE;                     // slots before the tile (n <= 64 reaches t - 63)
-static_assert(GL_TILE % GL_NT == 0 && GL_NT % WAVE == 0 && GL_H == WAVE && BQ_BB_STABLE_MAX_N <= GL_H,
-              "mask words are whole waves of slots; wave 0 fills the halo");
+constexpr int GL_TILE = CT_TILE, GL_NT = CT_NT, GL_CPT = CT_CPT;   // the kernel's names for the geometry
+constexpr int GL_H = WAVE;   // slots before the tile (n <= 64 reaches t - 63)
+static_assert(GL_H == WAVE && BQ_BB_STABLE_MAX_N <= GL_H, "mask words are whole waves of slots; wave 0 fills the halo");
 
 struct GlArgs {
   const double *close, *bbu, *bbm, *bbl;    // current_price; the frame's bands
@@ -234,9 +232,10 @@ extern "C" int bq_grid_ladder_replay(const double* close, int64_t ld_c, const do
                                      double* const* values, int64_t ld_out, void* stream) {
   using namespace bq;
   const bool own_bands = bb_high || bb_mid_arg || bb_low;
+  int64_t tiles;
   if (!close || !bb_upper || !bb_mid || !bb_lower || !market_regime || !long_regime_score || !status || S < 0 ||
       T < 0 || ld_c < T || ld_bb < T || ld_out < T || (ld_sym != 0 && ld_sym < T) || (ctx_T != 1 && ctx_T != T) ||
-      T > 0x7fffffff - 2 * GL_TILE)
+      !candle_tiles(S, T, tiles))
     return BQ_EINVAL;
   if (own_bands && (!bb_high || !bb_mid_arg || !bb_low || ld_bands < T)) return BQ_EINVAL;
   if (sym_ok && (!sym_micro_regime || !sym_micro_transition || !sym_above_ema20 || !sym_above_ema50 ||
@@ -252,8 +251,6 @@ extern "C" int bq_grid_ladder_replay(const double* close, int64_t ld_c, const do
                    p.atr_multiplier, p.min_long_score}))
     return BQ_EINVAL;
   if (S == 0 || T == 0) return BQ_OK;
-  const int64_t tiles = (T + GL_TILE - 1) / GL_TILE;
-  if (tiles * S > 0x7fffffff) return BQ_EINVAL;
   A.close = close;
   A.bbu = bb_upper;
   A.bbm = bb_mid;
@@ -285,7 +282,7 @@ extern "C" int bq_grid_ladder_replay(const double* close, int64_t ld_c, const do
   A.tiles = (int)tiles;
   A.ctx_T = (int)ctx_T;
   A.status = status;
-  for (int k = 0; k < BQ_GL_NVALUES; ++k) A.val[k] = values ? values[k] : nullptr;
+  tile_values(A.val, values);
   hipLaunchKernelGGL(grid_ladder_kernel, dim3((unsigned)(tiles * S)), dim3(GL_NT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? BQ_OK : BQ_EHIP;
 }

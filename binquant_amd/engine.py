@@ -1414,14 +1414,16 @@ def _common_pitch(cols: list[torch.Tensor]) -> tuple[list[torch.Tensor], int]:
     return cols, ld
 
 
-# ---- the argument layer of the nine replay wrappers (retest, spike_fade, price_tracker, mean_reversion,
-# range_fade, buy_the_dip, bb_extreme, rs_reversal, grid_ladder): each check raises the text the wrappers raised themselves, with the entry's name substituted
+# ---- the argument layer of the strategy entry points on a [S, T] panel: the tile-mapped entries (impulse_rider,
+# bb_stable, top_gainer_entry, sweep_select), spike_frames and the nine replay wrappers (retest, spike_fade,
+# price_tracker, mean_reversion, range_fade, buy_the_dip, bb_extreme, rs_reversal, grid_ladder). Each check raises the
+# text the wrappers raised themselves, with the entry's name substituted
 
-def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None) -> dict:
+def _replay_params(entry: str, defaults: dict, params: dict, int_keys=None, noun: str = "parameters") -> dict:
     """defaults overlaid with params; int_keys given: every other parameter is a finite float."""
     bad = set(params) - set(defaults)
     if bad:
-        raise ValueError(f"{entry}: unknown parameters {sorted(bad)} (known: {sorted(defaults)})")
+        raise ValueError(f"{entry}: unknown {noun} {sorted(bad)} (known: {sorted(defaults)})")
     par = {**defaults, **params}
     if int_keys is not None:
         for k, val in par.items():
@@ -1437,15 +1439,15 @@ def _replay_struct(cls, par: dict, int_keys):
     return p
 
 
-def _replay_columns(entry: str, columns, known) -> None:
+def _replay_columns(entry: str, columns, known, tail: bool = True) -> None:
     unknown = [k for k in columns if k not in known]
     if unknown:
-        raise ValueError(f"{entry}: unknown columns {unknown} (known: {known})")
+        raise ValueError(f"{entry}: unknown columns {unknown}" + (f" (known: {known})" if tail else ""))
 
 
-def _replay_shape(c) -> tuple[int, int]:
+def _replay_shape(c, name: str = "close") -> tuple[int, int]:
     if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
+        raise ValueError(f"{name}: expected [S, T] with unit stride along T")
     return c.shape
 
 
@@ -1456,6 +1458,26 @@ def _replay_panels(pairs, S: int, T: int) -> None:
             raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
         if tuple(x.shape) != (S, T):
             raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+
+
+_BOOL = (torch.bool,)
+
+
+def _replay_flags(pairs, S: int, T: int, dtypes=_BOOL, dev: bool = False, pitch: bool = False):
+    """(tensor, name) pairs: flag panels [S, T] of one of dtypes. dev False:
+    that check alone, on the host. dev True: each is on the device as well,
+    and they are returned with unit stride along T (a flag of another stride
+    is copied), each on its own row pitch; pitch: on one common row pitch,
+    as (flags, pitch)."""
+    for x, name in pairs:
+        if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or tuple(x.shape) != (S, T):
+            raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)}")
+        if dev and not x.is_cuda:
+            raise ValueError(f"{name}: expected a CUDA tensor (no CPU path)")
+    if not dev:
+        return None
+    flags = [x if T <= 1 or x.stride(1) == 1 else x.contiguous() for x, _ in pairs]
+    return _common_pitch(flags) if pitch else flags
 
 
 def _replay_features(features, names) -> list:
@@ -1519,7 +1541,8 @@ def _replay_state(state, names, dtypes, S: int):
 
 
 def _replay_rows(lens, first_t, from_t, S: int, dev=None):
-    """lens / first_t / from_t: gated on the host (dev None), or as int64 [S] on dev."""
+    """lens / first_t / from_t (None throughout for an entry without it): gated
+    on the host (dev None), or as int64 [S] on dev."""
     rows = zip((lens, first_t, from_t), ("lens", "first_t", "from_t"))
     if dev is None:
         return tuple(_gate_rows(v, name, S) for v, name in rows)
@@ -1555,36 +1578,24 @@ def impulse_rider(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Te
     that bench_ts ascends (ValueError otherwise; one small reduction read
     back to the host, skipped while a graph is being captured) — False for
     callers that built the benchmark frame themselves."""
-    bad = set(thresholds) - set(IMPULSE_DEFAULTS)
-    if bad:
-        raise ValueError(f"impulse_rider: unknown thresholds {sorted(bad)} (known: {sorted(IMPULSE_DEFAULTS)})")
-    par = {**IMPULSE_DEFAULTS, **thresholds}
+    par = _replay_params("impulse_rider", IMPULSE_DEFAULTS, thresholds, noun="thresholds")
     if int(par["min_history"]) < 7:
         raise ValueError("impulse_rider: min_history must be >= 7 (the stencil reaches t - 6)")
     columns = tuple(columns)
-    unknown = [k for k in columns if k not in _lib.IMPULSE_VALUES]
-    if unknown:
-        raise ValueError(f"impulse_rider: unknown columns {unknown}")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
-    for x, name in ((o, "open"), (h, "high"), (l, "low"), (c, "close"), (atr, "atr")):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    if not isinstance(open_time, torch.Tensor) or open_time.dtype != torch.int64 or tuple(open_time.shape) != (S, T):
-        raise ValueError(f"open_time: expected an int64 tensor of shape {(S, T)}")
+    _replay_columns("impulse_rider", columns, _lib.IMPULSE_VALUES, tail=False)
+    S, T = _replay_shape(c)
+    px = ((o, "open"), (h, "high"), (l, "low"), (c, "close"))
+    _replay_panels(px + ((atr, "atr"),), S, T)
+    _replay_time(open_time, "open_time", S, T)
     if not isinstance(bench_ts, torch.Tensor) or bench_ts.dtype != torch.int64 or bench_ts.dim() != 1:
         raise ValueError("bench_ts: expected a 1-D int64 tensor of ms timestamps")
     if not isinstance(bench_close, torch.Tensor) or bench_close.dtype != torch.float64 \
             or tuple(bench_close.shape) != tuple(bench_ts.shape):
         raise ValueError(f"bench_close: expected a float64 tensor of shape {tuple(bench_ts.shape)}")
-    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S)
     if not bench_ts.is_cuda and bench_ts.numel() > 1 and bool((bench_ts[1:] < bench_ts[:-1]).any()):
         raise ValueError("bench_ts: must be ascending")   # a host tensor: rejected without a device
-    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in ((o, "open"), (h, "high"), (l, "low"),
-                                                                 (c, "close"))])
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in px])
     atr = _check_panel(atr, "atr")
     ts = _check_ts(open_time, "open_time")
     bts = _check_ts(bench_ts, "bench_ts").reshape(-1)
@@ -1592,15 +1603,9 @@ def impulse_rider(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Te
     if check_bench:
         _check_ascending(bts)
     dev = c.device
-    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
-    p = _lib.BqImpulseParams()
-    for k in ("min_impulse", "max_impulse", "min_rs", "max_btc_return", "min_conf_return", "min_close_location",
-              "max_atr_pct", "entry_factor"):
-        setattr(p, k, float(par[k]))
-    p.min_history = int(par["min_history"])
-    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
-    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
-    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.IMPULSE_VALUES])
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S, dev)
+    p = _replay_struct(_lib.BqImpulseParams, par, ("min_history",))
+    status, outs, vals = _replay_outputs(columns, _lib.IMPULSE_VALUES, S, T, dev)
     st = _lib.load().bq_impulse_rider(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), ld_in, _ptr(atr),
                                       _row_stride(atr), _ptr(ts), T, _ptr(lens), _ptr(first_t), S, T, _ptr(bts),
                                       _ptr(bc), bts.numel(), ctypes.byref(p), _ptr(status), vals, T,
@@ -1630,19 +1635,13 @@ def bb_stable(bb_upper: torch.Tensor, bb_mid: torch.Tensor, bb_lower: torch.Tens
     change=False)."""
     if not 1 <= int(n) <= _lib.BB_STABLE_MAX_N:
         raise ValueError(f"bb_stable: n must be in 1..{_lib.BB_STABLE_MAX_N}, got {n}")
-    if not isinstance(bb_mid, torch.Tensor) or bb_mid.dim() != 2:
-        raise ValueError("bb_mid: expected [S, T] with unit stride along T")
-    S, T = bb_mid.shape
-    for x, name in ((bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower")):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
-    cols, ld_in = _common_pitch([_check_panel(x, nm) for x, nm in ((bb_upper, "bb_upper"), (bb_mid, "bb_mid"),
-                                                                   (bb_lower, "bb_lower"))])
+    S, T = _replay_shape(bb_mid, "bb_mid")
+    bb = ((bb_upper, "bb_upper"), (bb_mid, "bb_mid"), (bb_lower, "bb_lower"))
+    _replay_panels(bb, S, T)
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S)
+    cols, ld_in = _common_pitch([_check_panel(x, nm) for x, nm in bb])
     dev = bb_mid.device
-    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S, dev)
     stable = torch.empty((S, T), dtype=torch.bool, device=dev)
     chg = torch.empty((S, T), dtype=torch.float64, device=dev) if change else None
     st = _lib.load().bq_bb_stable(_ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ld_in, _ptr(lens), _ptr(first_t), S, T,
@@ -1678,52 +1677,33 @@ def top_gainer_entry(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch
     are UNROUNDED — the reference's round_numbers(.., 4) is the host's step —
     and NaN except where status is 0 or risk_rejected. thresholds:
     TOP_GAINER_DEFAULTS' keys."""
-    bad = set(thresholds) - set(TOP_GAINER_DEFAULTS)
-    if bad:
-        raise ValueError(f"top_gainer_entry: unknown thresholds {sorted(bad)} (known: {sorted(TOP_GAINER_DEFAULTS)})")
-    par = {**TOP_GAINER_DEFAULTS, **thresholds}
+    par = _replay_params("top_gainer_entry", TOP_GAINER_DEFAULTS, thresholds, noun="thresholds")
     if int(par["min_history"]) < 25:
         raise ValueError("top_gainer_entry: min_history must be >= 25 (the returns reach t - 24)")
     for k in ("lookback_high", "volume_window", "full_extension_bars"):
         if not 1 <= int(par[k]) <= _lib.TGE_MAX_LOOKBACK:
             raise ValueError(f"top_gainer_entry: {k} must be in 1..{_lib.TGE_MAX_LOOKBACK}, got {par[k]}")
     columns = tuple(columns)
-    unknown = [k for k in columns if k not in _lib.TGE_VALUES]
-    if unknown:
-        raise ValueError(f"top_gainer_entry: unknown columns {unknown}")
-    if not isinstance(c, torch.Tensor) or c.dim() != 2:
-        raise ValueError("close: expected [S, T] with unit stride along T")
-    S, T = c.shape
+    _replay_columns("top_gainer_entry", columns, _lib.TGE_VALUES, tail=False)
+    S, T = _replay_shape(c)
     named = [(o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume")]
     named += [(x, n) for x, n in ((qv, "quote_volume"), (atr, "atr")) if x is not None]
-    for x, name in named:
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
-    if risk_ok is not None and (not isinstance(risk_ok, torch.Tensor) or risk_ok.dtype != torch.bool
-                                or tuple(risk_ok.shape) != (S, T)):
-        raise ValueError(f"risk_ok: expected a bool tensor of shape {(S, T)}")
-    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
+    _replay_panels(named, S, T)
+    risk = [(risk_ok, "risk_ok")] if risk_ok is not None else []
+    _replay_flags(risk, S, T)
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S)
     cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in named[:5]])
     qv = _check_panel(qv, "quote_volume") if qv is not None else None
     atr = _check_panel(atr, "atr") if atr is not None else None
-    if risk_ok is not None:
-        if not risk_ok.is_cuda:
-            raise ValueError("risk_ok: expected a CUDA tensor (no CPU path)")
-        if T > 1 and risk_ok.stride(1) != 1:
-            risk_ok = risk_ok.contiguous()
+    if risk:
+        (risk_ok,) = _replay_flags(risk, S, T, dev=True)   # on its own row pitch
     dev = c.device
-    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
-    p = _lib.BqTopGainerParams()
-    for k, val in par.items():
-        setattr(p, k, int(val) if k in _TG_INT_PARAMS else float(val))
-    status = torch.empty((S, T), dtype=torch.uint8, device=dev)
-    entry = torch.empty((S, T), dtype=torch.uint8, device=dev)
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S, dev)
+    p = _replay_struct(_lib.BqTopGainerParams, par, _TG_INT_PARAMS)
+    status, outs, vals = _replay_outputs(columns, _lib.TGE_VALUES, S, T, dev)
+    entry = torch.empty_like(status)
     sc = torch.empty((S, T), dtype=torch.float64, device=dev)
-    sl = torch.empty((S, T), dtype=torch.float64, device=dev)
-    outs = {k: torch.empty((S, T), dtype=torch.float64, device=dev) for k in columns}
-    vals = _lib.ptr_array([outs[k].data_ptr() if k in outs else 0 for k in _lib.TGE_VALUES])
+    sl = torch.empty_like(sc)
     st = _lib.load().bq_top_gainer_entry(
         _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), ld_in, _ptr(qv),
         _row_stride(qv) if qv is not None else T, _ptr(atr), _row_stride(atr) if atr is not None else T,
@@ -1754,46 +1734,29 @@ def sweep_select(cols, score_cross: torch.Tensor, *, route_ok: torch.Tensor | No
     caller's tensors ([S, T] with one row pitch; [T]). Large panels get their
     [S, T] outputs on enrich_outputs' padded pitch. thresholds:
     SWEEP_DEFAULTS' keys."""
-    bad = set(thresholds) - set(SWEEP_DEFAULTS)
-    if bad:
-        raise ValueError(f"sweep_select: unknown thresholds {sorted(bad)} (known: {sorted(SWEEP_DEFAULTS)})")
-    par = {**SWEEP_DEFAULTS, **thresholds}
+    par = _replay_params("sweep_select", SWEEP_DEFAULTS, thresholds, noun="thresholds")
     cols = list(cols)
     if len(cols) != len(_lib.SW_COLUMNS):
         raise ValueError(f"sweep_select: expected the {len(_lib.SW_COLUMNS)} columns {_lib.SW_COLUMNS}")
-    if not isinstance(cols[0], torch.Tensor) or cols[0].dim() != 2:
-        raise ValueError(f"{_lib.SW_COLUMNS[0]}: expected [S, T] with unit stride along T")
-    S, T = cols[0].shape
-    for x, name in zip(cols, _lib.SW_COLUMNS):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected dtype float64, got {getattr(x, 'dtype', type(x))}")
-        if tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: shape {tuple(x.shape)} != {(S, T)}")
+    S, T = _replay_shape(cols[0], _lib.SW_COLUMNS[0])
+    named = list(zip(cols, _lib.SW_COLUMNS))
+    _replay_panels(named, S, T)
     masks = [(score_cross, "score_cross")] + ([(route_ok, "route_ok")] if route_ok is not None else [])
-    for m, name in masks:
-        if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or tuple(m.shape) != (S, T):
-            raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)}")
-        if not m.is_cuda:
-            raise ValueError(f"{name}: expected a CUDA tensor (no CPU path)")
+    masks = _replay_flags(masks, S, T, dev=True)   # each on its own row pitch
+    score_cross, route_ok = masks[0], (masks[1] if route_ok is not None else None)
     if symbol_rank is not None and (not isinstance(symbol_rank, torch.Tensor) or symbol_rank.dtype != torch.int32
                                     or symbol_rank.numel() != S or not symbol_rank.is_cuda):
         raise ValueError(f"symbol_rank: expected an int32 CUDA tensor of {S} entries")
     t_lo, t_hi = (0, T) if t_range is None else (int(t_range[0]), int(t_range[1]))
     if not 0 <= t_lo <= t_hi <= T:
         raise ValueError(f"t_range: expected 0 <= t_lo <= t_hi <= {T}, got {(t_lo, t_hi)}")
-    lens, first_t = _gate_rows(lens, "lens", S), _gate_rows(first_t, "first_t", S)
-    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in zip(cols, _lib.SW_COLUMNS)])
-    score_cross = score_cross if T <= 1 or score_cross.stride(1) == 1 else score_cross.contiguous()
-    if route_ok is not None and T > 1 and route_ok.stride(1) != 1:
-        route_ok = route_ok.contiguous()
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S)
+    cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in named])
     dev = cols[0].device
-    lens, first_t = _check_lens(lens, S, dev), _check_lens(first_t, S, dev)
+    lens, first_t, _ = _replay_rows(lens, first_t, None, S, dev)
     if symbol_rank is not None:
         symbol_rank = symbol_rank.reshape(S).contiguous()
-    p = _lib.BqSweepParams()
-    for k in ("min_momentum_atr", "max_momentum_atr", "min_close_location"):
-        setattr(p, k, float(par[k]))
-    p.min_frame = int(par["min_frame"])
+    p = _replay_struct(_lib.BqSweepParams, par, ("min_frame",))
     if out is None:
         pad = ENRICH_ROW_PAD if S >= 1024 and T >= 1024 else 0
         status = torch.empty((S, T + pad), dtype=torch.uint8, device=dev)[:, :T]
@@ -1853,18 +1816,14 @@ def retest_replay(o: torch.Tensor, h: torch.Tensor, l: torch.Tensor, c: torch.Te
     px = ((o, "open"), (h, "high"), (l, "low"), (c, "close"), (ema, "ema"))
     _replay_panels(px, S, T)
     _replay_time(open_time, "open_time", S, T)
-    flags = [leader] if risk_ok is None else [leader, risk_ok]
-    for x, name in zip(flags, ("leader", "risk_ok")):
-        if not isinstance(x, torch.Tensor) or x.dtype != torch.bool or tuple(x.shape) != (S, T):
-            raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)}")
+    flags = [(leader, "leader")] + ([(risk_ok, "risk_ok")] if risk_ok is not None else [])
+    _replay_flags(flags, S, T)
     lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
     sa, ss, sl = _replay_state(state, ("active", "started", "level"), (torch.uint8, torch.int64, torch.float64), S)
     cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in px])
     ts = _check_ts(open_time, "open_time")
-    _replay_on_device("leader / risk_ok / state", flags + [sa, ss, sl])
-    if any(f.shape[1] > 1 and f.stride(1) != 1 for f in flags):
-        flags = [f.contiguous() for f in flags]
-    flags, ld_b = _common_pitch(flags)
+    _replay_on_device("leader / risk_ok / state", [f for f, _ in flags] + [sa, ss, sl])
+    flags, ld_b = _replay_flags(flags, S, T, dev=True, pitch=True)
     dev = c.device
     lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
     p = _lib.BqRetestParams(int(par["watch_ms"]), mh, L, float(par["support_factor"]), float(par["pullback_factor"]))
@@ -1913,13 +1872,12 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
     px = ((o, "open"), (h, "high"), (c, "close"))
     _replay_panels(px, S, T)
     _replay_time(open_time, "open_time", S, T)
-    if not isinstance(source_ok, torch.Tensor) or source_ok.dtype != torch.bool or tuple(source_ok.shape) != (S, T):
-        raise ValueError(f"source_ok: expected a bool tensor of shape {(S, T)}")
-    for m, name in ((src_market, "src_market"), (fail_market, "fail_market")):
-        if m is not None and (not isinstance(m, torch.Tensor) or m.dtype != torch.bool
-                              or tuple(m.shape) not in ((S, T), (T,))):
+    _replay_flags([(source_ok, "source_ok")], S, T)
+    masks = [(m, name) for m, name in ((src_market, "src_market"), (fail_market, "fail_market")) if m is not None]
+    for m, name in masks:   # written out: a gate may be one [T] row shared by all symbols
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.bool or tuple(m.shape) not in ((S, T), (T,)):
             raise ValueError(f"{name}: expected a bool tensor of shape {(S, T)} or {(T,)}")
-    shared = [m.dim() == 1 for m in (src_market, fail_market) if m is not None]
+    shared = [m.dim() == 1 for m, _ in masks]
     if len(set(shared)) > 1:
         raise ValueError("src_market / fail_market: both [S, T] or both [T] (they share one row stride)")
     lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
@@ -1927,17 +1885,15 @@ def spike_fade_replay(o: torch.Tensor, h: torch.Tensor, c: torch.Tensor, open_ti
                                    (torch.uint8, torch.int64, torch.float64, torch.float64), S)
     cols, ld_in = _common_pitch([_check_panel(x, n) for x, n in px])
     ts = _check_ts(open_time, "open_time")
-    masks = [m for m in (src_market, fail_market) if m is not None]
-    _replay_on_device("source_ok / src_market / fail_market / state", [source_ok] + masks + [sa, so, sh, sc])
-    if T > 1 and source_ok.stride(1) != 1:
-        source_ok = source_ok.contiguous()
-    ld_m = T
-    if masks and shared[0]:
-        masks, ld_m = [m.contiguous() for m in masks], 0
-    elif masks:
-        if any(m.shape[1] > 1 and m.stride(1) != 1 for m in masks):
-            masks = [m.contiguous() for m in masks]
-        masks, ld_m = _common_pitch(masks)
+    _replay_on_device("source_ok / src_market / fail_market / state",
+                      [source_ok] + [m for m, _ in masks] + [sa, so, sh, sc])
+    (source_ok,) = _replay_flags([(source_ok, "source_ok")], S, T, dev=True)   # on its own row pitch
+    if not masks:
+        ld_m = T
+    elif shared[0]:
+        masks, ld_m = [m.contiguous() for m, _ in masks], 0
+    else:
+        masks, ld_m = _replay_flags(masks, S, T, dev=True, pitch=True)
     masks = iter(masks)
     sm = next(masks) if src_market is not None else None
     fm = next(masks) if fail_market is not None else None
@@ -2023,17 +1979,12 @@ def spike_frames(cols: dict, params, *, first_t=None, lens=None, from_t=None, al
         raise ValueError(f"spike_frames: T = {T} exceeds the cap of {SPIKE_FRAMES_MAX_T} candles per row")
     fin = [(cols[k], k) for k in _lib.SPIKE_FRAMES_IN]
     _replay_panels(fin, S, T)
-    for k in _lib.SPIKE_FRAMES_IN_B:
-        x = cols[k]
-        if not isinstance(x, torch.Tensor) or x.dtype not in (torch.bool, torch.uint8) or tuple(x.shape) != (S, T):
-            raise ValueError(f"{k}: expected a bool tensor of shape {(S, T)}")
+    bflags = [(cols[k], k) for k in _lib.SPIKE_FRAMES_IN_B]
+    _replay_flags(bflags, S, T, (torch.bool, torch.uint8))
     lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S)
     fcols, ld_in = _common_pitch([_check_panel(x, n) for x, n in fin])
-    bcols = [cols[k] for k in _lib.SPIKE_FRAMES_IN_B]
-    _replay_on_device("spike_frames: flag inputs", bcols)
-    if any(T > 1 and x.stride(1) != 1 for x in bcols):
-        bcols = [x.contiguous() for x in bcols]
-    bcols, ld_b = _common_pitch(bcols)
+    _replay_on_device("spike_frames: flag inputs", [x for x, _ in bflags])
+    bcols, ld_b = _replay_flags(bflags, S, T, (torch.bool, torch.uint8), dev=True, pitch=True)
     dev = fcols[0].device
     lens, first_t, from_t = _replay_rows(lens, first_t, from_t, S, dev)
     out = {k: torch.empty((S, T), dtype=torch.float64 if k in SPIKE_FRAME_FLOAT else torch.bool, device=dev)

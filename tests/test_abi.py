@@ -92,6 +92,40 @@ def test_roll_job_rows_validated_without_device():
     assert call(job(_lib.ROLL_EWM, 1, alpha=0.0)) == _lib.BQ_EINVAL    # alpha still checked
 
 
+def test_candle_tile_entries_rejected_without_device():
+    """bq_impulse_rider, bq_bb_stable and bq_grid_ladder_replay share one tile
+    geometry and one grid check: a row pitch below T, T above the cap
+    (2^31 - 1 - 2 tiles) and S * tiles past 2^31 - 1 are BQ_EINVAL, S == 0 or
+    T == 0 is BQ_OK — before any HIP call (fake, never dereferenced pointers)."""
+    from binquant_amd import _lib
+
+    lib = _lib.load()
+    x, null = 0x10000, ctypes.c_void_p()
+    tile = _lib.IMPULSE_TILE
+    assert tile == _lib.GRID_LADDER_TILE
+
+    def rider(S, T, ld):
+        return lib.bq_impulse_rider(x, x, x, x, ld, x, ld, x, ld, None, None, S, T, x, x, 10, None, x, None, ld, null)
+
+    def stable(S, T, ld):
+        return lib.bq_bb_stable(x, x, x, ld, None, None, S, T, 8, 20.0, x, None, ld, null)
+
+    def ladder(S, T, ld):
+        return lib.bq_grid_ladder_replay(x, ld, x, x, x, ld, None, None, None, 0, None, None, x, x, 1, None, None, None,
+                                         None, None, None, None, 0, None, None, None, S, T, None, x, None, ld, null)
+
+    cap = 0x7fffffff - 2 * tile
+    for name, call in (("impulse_rider", rider), ("bb_stable", stable), ("grid_ladder_replay", ladder)):
+        assert call(4, 100, 99) == _lib.BQ_EINVAL, name                    # ld < T
+        assert call(1, cap + 1, cap + 1) == _lib.BQ_EINVAL, name           # T above the cap
+        assert call(0, cap + 1, cap + 1) == _lib.BQ_EINVAL, name           # also with no rows: the checks come first
+        assert call(1 << 21, 1024 * tile, 1024 * tile) == _lib.BQ_EINVAL, name   # 2^21 rows x 1024 tiles = 2^31
+        assert call(1 << 31, 100, 100) == _lib.BQ_EINVAL, name
+        assert call(0, 100, 100) == _lib.BQ_OK, name
+        assert call(0, cap, cap) == _lib.BQ_OK, name                       # the cap itself is accepted
+        assert call(4, 0, 0) == _lib.BQ_OK, name
+
+
 def test_missing_library_fails_loudly(tmp_path):
     from binquant_amd import _lib
 
