@@ -240,6 +240,18 @@ SPIKE_FRAMES_IN_B = ("accel_spike_flag", "accel_spike_short_flag", "upward", "do
 SPIKE_FRAMES_OUT = ("label", "label_pre", "label_short", "label_short_pre", "volume_cluster_flag", "price_break_flag",
                     "cumulative_price_break_flag", "cumulative_price_break_short_flag", "accel_spike_flag",
                     "accel_spike_short_flag", "upward", "downward")
+# bq_spike_frames_capped: the smallest frame_cap (BQ_SPIKE_FRAMES_MIN_CAP; the largest is SPIKE_FRAMES_MAX_T) and the
+# int32 columns (enum bq_spike_frames_in_i)
+SPIKE_FRAMES_MIN_CAP = 64
+SPIKE_FRAMES_IN_I = ("dyn_src", "close_next")
+
+
+class BqSpikeFramesCap(ctypes.Structure):
+    """Mirror of ``bq_spike_frames_cap`` (include/binquant_amd.h)."""
+
+    _fields_ = [("frame_cap", ctypes.c_int32), ("base_window", ctypes.c_int32),
+                ("accel_volume_deriv_window", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("price_break_dynamic_q", ctypes.c_double)]
 
 
 # bq_spike_fade_replay: event codes (BQ_FS_*), detail bits (BQ_FS_D_*)
@@ -532,6 +544,10 @@ SIGNATURES: dict[str, tuple] = {
     "bq_spike_frames": (ctypes.c_int, [_PP, _I64, _PP, _I64, _I32, _P, _P, _P, _I64, _I64,
                                        ctypes.POINTER(BqSpikeFramesParams), _P, ctypes.c_size_t, _P, _P, _PP, _I64,
                                        _P]),
+    "bq_spike_frames_capped_workspace": (ctypes.c_size_t, [_I64, _I64]),
+    "bq_spike_frames_capped": (ctypes.c_int, [_PP, _I64, _PP, _I64, _PP, _I64, _I32, _P, _P, _P, _I64, _I64,
+                                              ctypes.POINTER(BqSpikeFramesParams), ctypes.POINTER(BqSpikeFramesCap),
+                                              _P, ctypes.c_size_t, _P, _P, _PP, _I64, _P]),
     "bq_price_tracker_default_params": (None, [ctypes.POINTER(BqPriceTrackerParams)]),
     "bq_price_tracker_replay": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64,
                                                _P, _I64, _P, _I64, _P, _P, _P, _I64, _I64,

@@ -41,25 +41,9 @@
 //   forward replay then re-evaluates from the run. The long and the short
 //   label are walked separately, as the method does.
 //   Resource usage (gfx950 cross-compile, -O3): see DESIGN.md §4.29.
-#include "bq_replay.h"
-#include "binquant_amd.h"
+#include "bq_spikeframes.h"
 
 namespace bq {
-
-constexpr int SF_QNT = 2 * WAVE;   // the quantile kernel: one wave per column
-
-struct SpikeFramesArgs {
-  const double* in[BQ_NUM_SPIKE_FRAMES_IN];
-  const uint8_t* in_b[BQ_NUM_SPIKE_FRAMES_IN_B];
-  const int64_t *lens, *first, *from;
-  int64_t ld_in, ld_b, ld_out, S;
-  int T, aligned, cap, omask;
-  bq_spike_frames_params p;
-  double *qv, *qp;   // workspace: the raw prefix quantiles [S][T]
-  int* first_obs;    // workspace: [S][2] the first observed candle of each column (T: none)
-  double *vcmr, *pbbt;
-  uint8_t* out_b[BQ_NUM_SPIKE_FRAMES_OUT];
-};
 
 __global__ __launch_bounds__(SF_QNT) void spike_prefix_quantile_kernel(const SpikeFramesArgs A) {
   extern __shared__ uint64_t sf_keys[];
@@ -119,114 +103,6 @@ __global__ __launch_bounds__(SF_QNT) void spike_prefix_quantile_kernel(const Spi
     if (in && t >= from) qo[t] = res;
   }
   if (lane == 0) *fo_out = fo;
-}
-
-enum { SF_VCF = 1, SF_PBF = 2, SF_CUM = 4, SF_CUMS = 8, SF_PRE = 16, SF_SPRE = 32 };
-
-// the row's input columns, offset so that [u] is candle u of the panel
-struct SpikeFramesRow {
-  const double *vr, *pca, *dyn, *bsp, *cp, *cn, *op, *cl;
-  const uint8_t *acc, *accs;
-  int first;
-};
-
-// The flag bits of row u of the frame [first, tend] under (vc, pb)
-// (apply_preliminary_label, :350-488); 0 outside the frame.
-template <class K>
-__device__ __forceinline__ unsigned spike_eval(const SpikeFramesRow& P, K k, int u, int tend, double vc, double pb) {
-  if (u < P.first || u > tend) return 0u;
-  const int vw = k->p.volume_cluster_window, mc = k->p.volume_cluster_min_count;
-  const int cw = k->p.cumulative_price_window, mode = k->p.label_mode;
-  const double vc8 = vc * 0.8;
-  // bit j: volume_ratio >= vc (m) / >= 0.8 vc (m8) at candle u + 1 - j; a candle outside the frame has no bit
-  const int nb = vw + 2 > cw + 1 ? vw + 2 : cw + 1;   // <= 32
-  unsigned m = 0u, m8 = 0u;
-  for (int j = 0; j < nb; ++j) {
-    const int w = u + 1 - j;
-    if (w >= P.first && w <= tend) {
-      const double x = P.vr[w];
-      m |= (x >= vc ? 1u : 0u) << j;
-      m8 |= (x >= vc8 ? 1u : 0u) << j;
-    }
-  }
-  // rolling(vw, min_periods=1).sum() >= mc, and the row's own condition (:351-353)
-  const unsigned wmask = (1u << vw) - 1u;
-  const bool base_n = (m & 1u) && __popc(m & wmask) >= mc;                  // row u + 1 (none at u == tend)
-  const bool base_u = ((m >> 1) & 1u) && __popc((m >> 1) & wmask) >= mc;
-  const bool base_p = ((m >> 2) & 1u) && __popc((m >> 2) & wmask) >= mc;    // row u - 1
-  const bool vcf = mode == 0 ? base_u && !base_n : mode == 1 ? base_u && !base_p : base_u;
-  // max(pb, dyn).ffill() == max(pb, ffill(dyn)); NaN until the quantile's first value (:395-399)
-  const double d = P.dyn[u];
-  const bool pbf = d == d && P.pca[u] >= (pb > d ? pb : d);
-  // (volume_ratio >= 0.8 vc).rolling(cw).max().astype(bool): NaN -> True on the first cw - 1 rows (:412-417)
-  const bool volc = u - P.first < cw - 1 || ((m8 >> 1) & ((1u << cw) - 1u)) != 0u;
-  const double cth = k->p.cumulative_price_threshold;
-  const bool cum = P.cp[u] >= cth && volc, cums = P.cn[u] >= cth && volc;
-  const bool combo = k->p.require_both_patterns ? vcf && pbf : vcf || pbf;
-  const double o = P.op[u], c = P.cl[u];
-  const double bmin = k->p.body_size_pct_min;
-  const bool big = bmin > 0.0 ? P.bsp[u] >= bmin : true;
-  const bool pre = (combo || cum || P.acc[u] != 0) && (!k->p.require_bullish_spike || c > o) && big;
-  const bool spre = (combo || cums || P.accs[u] != 0) && c < o && big;
-  return (vcf ? SF_VCF : 0) | (pbf ? SF_PBF : 0) | (cum ? SF_CUM : 0) | (cums ? SF_CUMS : 0) | (pre ? SF_PRE : 0) |
-         (spre ? SF_SPRE : 0);
-}
-
-// apply_cooldown on the frame [first, t] under (vc, pb), for its last row, whose
-// label bit `side` is set: kept or not. Wave-uniform arguments and result.
-template <class K>
-__device__ __forceinline__ bool spike_cooldown_keeps(const SpikeFramesRow& P, K k, int t, double vc, double pb,
-                                                     unsigned side, int bars, int lane) {
-  const int first = P.first;
-  const int ub0 = t - (WAVE - 1);
-  const uint64_t M0 = __ballot((spike_eval(P, k, ub0 + lane, t, vc, pb) & side) != 0u);   // bit 63: row t
-  // back from t - 1 to the nearest run of `bars` clear rows (rows before the frame are clear)
-  uint64_t cur = M0;
-  int ub = ub0, pos = WAVE - 1, clean = 0, start = first;
-  bool found = false;
-  for (;;) {
-    for (;;) {
-      const uint64_t sub = pos >= 64 ? cur : cur & ((1ull << pos) - 1ull);
-      const int hi = sub ? 63 - __builtin_clzll(sub) : -1;
-      const int zeros = pos - 1 - hi;
-      if (clean + zeros >= bars) {
-        start = ub + hi + 1;
-        found = true;
-        break;
-      }
-      if (hi < 0) {
-        clean += zeros;
-        break;
-      }
-      clean = 0;
-      pos = hi;
-    }
-    if (found || ub <= first) break;
-    ub -= WAVE;
-    pos = WAVE;
-    cur = __ballot((spike_eval(P, k, ub + lane, t, vc, pb) & side) != 0u);
-  }
-  if (!found || start < first) start = first;
-  // the greedy rule forward from `start` (:506-518)
-  int last = -0x40000000;
-  if (start >= ub0) {   // inside the first block: its mask is at hand
-    uint64_t m = M0 & (~0ull << (start - ub0));
-    while (m) {
-      const int i = __builtin_ctzll(m);
-      m &= m - 1;
-      if (ub0 + i - last > bars) last = ub0 + i;
-    }
-  } else {
-    for (int fb = start; fb <= t; fb += WAVE) {
-      uint64_t m = __ballot((spike_eval(P, k, fb + lane, t, vc, pb) & side) != 0u);
-      while (m) {
-        const int i = __builtin_ctzll(m);
-        m &= m - 1;
-        if (fb + i - last > bars) last = fb + i;
-      }
-    }
-  }
-  return last == t;
 }
 
 __global__ __launch_bounds__(RP_NT) void spike_frames_kernel(const SpikeFramesArgs A) {
@@ -348,46 +224,14 @@ extern "C" int bq_spike_frames(const double* const* in, int64_t ld_in, const uin
                                size_t workspace_bytes, double* vcmr, double* pbbt, uint8_t* const* out_b,
                                int64_t ld_out, void* stream) {
   using namespace bq;
-  if (!in || !in_b || S < 0 || T < 0 || ld_in < T || ld_b < T || ld_out < T || T > BQ_SPIKE_FRAMES_MAX_T)
-    return BQ_EINVAL;
   SpikeFramesArgs A;
-  for (int j = 0; j < BQ_NUM_SPIKE_FRAMES_IN; ++j)
-    if (!(A.in[j] = in[j])) return BQ_EINVAL;
-  for (int j = 0; j < BQ_NUM_SPIKE_FRAMES_IN_B; ++j)
-    if (!(A.in_b[j] = in_b[j])) return BQ_EINVAL;
-  if (params) A.p = *params;
-  else bq_spike_frames_default_params(&A.p);
-  const bq_spike_frames_params& p = A.p;
-  if (p.volume_cluster_window < 1 || p.volume_cluster_window > BQ_SPIKE_FRAMES_MAX_WINDOW ||
-      p.cumulative_price_window < 2 || p.cumulative_price_window > BQ_SPIKE_FRAMES_MAX_WINDOW ||
-      p.volume_cluster_min_count < 0 || p.label_mode < 0 || p.label_mode > 2 ||
-      p.post_spike_cooldown_bars >= BQ_SPIKE_FRAMES_MAX_COOLDOWN ||
-      !(p.volume_quantile >= 0.0 && p.volume_quantile <= 1.0) ||
-      !(p.price_base_floor_quantile >= 0.0 && p.price_base_floor_quantile <= 1.0) ||
-      !all_finite({p.cumulative_price_threshold, p.body_size_pct_min, p.volume_cluster_min_ratio,
-                   p.price_break_base_threshold, p.min_volume_ratio, p.min_price_abs_floor}))
-    return BQ_EINVAL;
+  const int st0 = spike_frames_setup(A, in, ld_in, in_b, ld_b, aligned, lens, first_t, from_t, S, T,
+                                     BQ_SPIKE_FRAMES_MAX_T, params, vcmr, pbbt, out_b, ld_out);
+  if (st0 != BQ_OK) return st0;
   if (S == 0 || T == 0) return BQ_OK;
   if (!workspace || workspace_bytes < bq_spike_frames_workspace(S, T) || ((uintptr_t)workspace & 7)) return BQ_EINVAL;
   int64_t blocks;
   if (!replay_blocks(S, blocks) || S > 0x7fffffff) return BQ_EINVAL;
-  A.omask = 0;
-  for (int j = 0; j < BQ_NUM_SPIKE_FRAMES_OUT; ++j) {
-    A.out_b[j] = out_b ? out_b[j] : nullptr;
-    A.omask |= A.out_b[j] ? 1 << j : 0;
-  }
-  A.vcmr = vcmr;
-  A.pbbt = pbbt;
-  A.omask |= (vcmr ? 1 << BQ_NUM_SPIKE_FRAMES_OUT : 0) | (pbbt ? 1 << (BQ_NUM_SPIKE_FRAMES_OUT + 1) : 0);
-  A.lens = lens;
-  A.first = first_t;
-  A.from = from_t;
-  A.ld_in = ld_in;
-  A.ld_b = ld_b;
-  A.ld_out = ld_out;
-  A.S = S;
-  A.T = (int)T;
-  A.aligned = aligned ? 1 : 0;
   A.cap = (int)((T + WAVE - 1) / WAVE) * WAVE;
   A.qv = (double*)workspace;
   A.qp = A.qv + S * T;

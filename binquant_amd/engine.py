@@ -1949,9 +1949,25 @@ def spike_frames_params(params) -> "_lib.BqSpikeFramesParams":
                                     bars, 0, *floats.values())
 
 
+def spike_frames_cap(params, frame_cap) -> "_lib.BqSpikeFramesCap":
+    """bq_spike_frames_cap from a frame_cap and the strategies.SpikeParams attributes that only the frame-local
+    columns need, checked against the kernel's range: ValueError outside it."""
+    lo, hi = _lib.SPIKE_FRAMES_MIN_CAP, SPIKE_FRAMES_MAX_T
+    if isinstance(frame_cap, bool) or not isinstance(frame_cap, int) or not lo <= frame_cap <= hi:
+        raise ValueError(f"spike_frames: frame_cap must be an int in {lo}..{hi} (or None: no cap), got {frame_cap!r}")
+    bw, aw = int(params.base_window), int(params.accel_volume_deriv_window)
+    if not (1 <= bw <= _lib.SPIKE_FRAMES_MAX_WINDOW and 1 <= aw <= _lib.SPIKE_FRAMES_MAX_WINDOW):
+        raise ValueError(f"spike_frames: base_window and accel_volume_deriv_window must be in "
+                         f"1..{_lib.SPIKE_FRAMES_MAX_WINDOW} under a frame_cap, got {(bw, aw)}")
+    q = float(params.price_break_dynamic_q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"spike_frames: price_break_dynamic_q must lie in [0, 1], got {q}")
+    return _lib.BqSpikeFramesCap(frame_cap, bw, aw, 0, q)
+
+
 @device_entry
 def spike_frames(cols: dict, params, *, first_t=None, lens=None, from_t=None, aligned: bool = False,
-                 columns=SPIKE_FRAME_COLUMNS) -> dict[str, torch.Tensor]:
+                 columns=SPIKE_FRAME_COLUMNS, frame_cap: int | None = None) -> dict[str, torch.Tensor]:
     """FailedSpikeFade.latest_signal() of every frame of a row
     (strategies/failed_spike_fade.py:229-594; bq_spike_frames): column t of
     row s = the method on a fresh instance whose frame is
@@ -1968,15 +1984,41 @@ def spike_frames(cols: dict, params, *, first_t=None, lens=None, from_t=None, al
     panel raises ValueError. Returns {name: [S, T]} for `columns`
     (SPIKE_FRAME_COLUMNS: latest_signal()'s flags as bool, the two calibrated
     thresholds as float64); False / NaN outside the formed candles. Allocates
-    by shape, reads nothing back."""
+    by shape, reads nothing back.
+
+    frame_cap = M (64 .. SPIKE_FRAMES_MAX_T; bq_spike_frames_capped): the
+    frame of column t is df.iloc[max(first_t[s], t + 1 - M):t + 1] instead, the
+    live store's sliding frame; T is then not limited (a frame's keys live in
+    LDS, whatever T). cols are still the columns of a frame starting at
+    first_t, with two int32 [S, T] columns beside them (_lib.SPIKE_FRAMES_IN_I;
+    strategies.spike_frame_columns(cap=True) forms them): dyn_src, the column
+    index of dyn_threshold's forward-fill source (-1: none), and close_next,
+    the index of the first valid close at or after the column (T: none). The
+    kernels restate what is frame-local near each frame's start (the header's
+    rule table); deeper rows agree with pandas to running-sum rounding.
+    frame_cap >= T is the uncapped call."""
     _replay_columns("spike_frames", columns, SPIKE_FRAME_COLUMNS)
     p = spike_frames_params(params)
+    cap = None if frame_cap is None else spike_frames_cap(params, frame_cap)
     missing = [k for k in _lib.SPIKE_FRAMES_IN + _lib.SPIKE_FRAMES_IN_B if k not in cols]
     if missing:
         raise ValueError(f"spike_frames: missing input columns {missing}")
     S, T = _replay_shape(cols["close"])
-    if T > SPIKE_FRAMES_MAX_T:
+    if cap is not None and frame_cap >= T:   # no frame slides
+        cap = None
+    if cap is None and T > SPIKE_FRAMES_MAX_T:
         raise ValueError(f"spike_frames: T = {T} exceeds the cap of {SPIKE_FRAMES_MAX_T} candles per row")
+    names_i = _lib.SPIKE_FRAMES_IN_I if cap is not None else ()
+    if cap is not None:
+        missing = [k for k in names_i if k not in cols]
+        if missing:
+            raise ValueError(f"spike_frames: missing input columns {missing} (frame_cap needs them)")
+        for k in names_i:
+            x = cols[k]
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.int32:
+                raise ValueError(f"{k}: expected dtype int32, got {getattr(x, 'dtype', type(x))}")
+            if tuple(x.shape) != (S, T):
+                raise ValueError(f"{k}: shape {tuple(x.shape)} != {(S, T)}")
     fin = [(cols[k], k) for k in _lib.SPIKE_FRAMES_IN]
     _replay_panels(fin, S, T)
     bflags = [(cols[k], k) for k in _lib.SPIKE_FRAMES_IN_B]
@@ -1990,6 +2032,20 @@ def spike_frames(cols: dict, params, *, first_t=None, lens=None, from_t=None, al
     out = {k: torch.empty((S, T), dtype=torch.float64 if k in SPIKE_FRAME_FLOAT else torch.bool, device=dev)
            for k in SPIKE_FRAME_COLUMNS if k in columns}
     lib = _lib.load()
+    if cap is not None:
+        _replay_on_device("spike_frames: index inputs", [cols[k] for k in names_i])
+        icols = [cols[k].contiguous() for k in names_i]
+        nbytes = int(lib.bq_spike_frames_capped_workspace(S, T))
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        st = lib.bq_spike_frames_capped(
+            _lib.ptr_array([x.data_ptr() for x in fcols]), ld_in, _lib.ptr_array([x.data_ptr() for x in bcols]), ld_b,
+            _lib.ptr_array([x.data_ptr() for x in icols]), T, int(bool(aligned)), _ptr(lens), _ptr(first_t),
+            _ptr(from_t), S, T, ctypes.byref(p), ctypes.byref(cap), _ptr(ws), nbytes,
+            _ptr(out.get("volume_cluster_min_ratio")), _ptr(out.get("price_break_base_threshold")),
+            _lib.ptr_array([out[k].data_ptr() if k in out else 0 for k in _lib.SPIKE_FRAMES_OUT]), T,
+            _stream_handle(None))
+        _lib.check(st, "bq_spike_frames_capped")
+        return out
     nbytes = int(lib.bq_spike_frames_workspace(S, T))
     ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
     st = lib.bq_spike_frames(

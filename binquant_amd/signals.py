@@ -475,17 +475,19 @@ def spike_source_allows(label, price_break_flag, cumulative_price_break_flag, ac
 
 
 def spike_source_frames(o, h, l, c, v, qv, p=None, *, first_t=None, lens=None, from_t=None, exact: bool = True,
-                        max_candle_return: float = 0.06):
+                        max_candle_return: float = 0.06, frame_cap: int | None = None):
     """FailedSpikeFade.source_spike_allows on the message of EVERY candle:
     spike_source_allows over strategies.failed_spike_frames' columns, column t
     of row s from latest_signal() of a fresh instance on the frame
     df.iloc[first_t[s]:t + 1]. Returns (ok bool [S, T], reason uint8 [S, T]),
     ok ready for failed_spike_fade(source_ok=...); outside the formed candles
     ok is False (reason 1: no label there). p: strategies.SpikeParams; the
-    other arguments are failed_spike_frames'."""
+    other arguments are failed_spike_frames', frame_cap among them (the live
+    store's sliding frame: df.iloc[max(first_t[s], t + 1 - frame_cap):t + 1])."""
     from . import strategies
 
     f = strategies.failed_spike_frames(o, h, l, c, v, qv, p, first_t=first_t, lens=lens, from_t=from_t, exact=exact,
+                                       frame_cap=frame_cap,
                                        columns=("label", "price_break_flag", "cumulative_price_break_flag",
                                                 "accel_spike_flag", "close_open_ratio", "upward"))
     return spike_source_allows(f["label"], f["price_break_flag"], f["cumulative_price_break_flag"],

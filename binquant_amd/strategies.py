@@ -614,13 +614,18 @@ def _frame_aligned(x: torch.Tensor, first_t: torch.Tensor) -> torch.Tensor:
     return torch.where(idx < T, torch.gather(x, 1, idx.clamp(max=T - 1)), torch.full_like(x, NAN))
 
 
-def spike_frame_columns(o, c, v, p: SpikeParams | None = None, exact: bool = True) -> dict[str, torch.Tensor]:
+def spike_frame_columns(o, c, v, p: SpikeParams | None = None, exact: bool = True,
+                        cap: bool = False) -> dict[str, torch.Tensor]:
     """engine.spike_frames' inputs from contiguous [S, T] open / close /
     volume panels whose frames start at column 0: the columns of
     FailedSpikeFade.detect() that no calibrated threshold enters
     (_lib.SPIKE_FRAMES_IN / SPIKE_FRAMES_IN_B's names) and close_open_ratio.
     The close's ffill, two fused element-wise programs around one batched
-    rolling call, the acceleration flags and the quantile's ffill."""
+    rolling call, the acceleration flags and the quantile's ffill. cap=True:
+    also the two int32 index columns a frame_cap needs
+    (_lib.SPIKE_FRAMES_IN_I): dyn_src, a running maximum over the unfilled
+    quantile's valid columns, and close_next, a reversed running minimum over
+    the close's."""
     p = p or SpikeParams()
     eps = 1e-6
     S, T = c.shape
@@ -644,14 +649,21 @@ def spike_frame_columns(o, c, v, p: SpikeParams | None = None, exact: bool = Tru
     acc = ((VR - F.shift(VR, aw)) >= p.accel_volume_deriv_min) & (PCA >= p.accel_price_change_min)
     a = F.run({"accel_spike_flag": acc & (PC > 0), "accel_spike_short_flag": acc & (PC < 0)}, S, T)
     (dyn_ff,) = engine.rolling_many(FF(dyn))   # max(floor, dyn).ffill() == max(floor, ffill(dyn)) (:395-398)
-    return {"volume_ratio": m["volume_ratio"], "price_change_abs": b["price_change_abs"], "dyn_threshold": dyn_ff,
+    cols = {"volume_ratio": m["volume_ratio"], "price_change_abs": b["price_change_abs"], "dyn_threshold": dyn_ff,
             "body_size_pct": b["body_size_pct"], "cum_pos": cum_pos, "cum_neg": cum_neg, "open": o, "close": c,
             "accel_spike_flag": a["accel_spike_flag"], "accel_spike_short_flag": a["accel_spike_short_flag"],
             "upward": m["upward"], "downward": m["downward"], "close_open_ratio": b["close_open_ratio"]}
+    if cap:
+        j = torch.arange(T, device=c.device, dtype=torch.int32).reshape(1, T).expand(S, T)
+        cols["dyn_src"] = torch.where(torch.isnan(dyn), torch.full_like(j, -1), j).cummax(1).values
+        nxt = torch.where(torch.isnan(c), torch.full_like(j, T), j)
+        cols["close_next"] = nxt.flip(1).cummin(1).values.flip(1).contiguous()
+    return cols
 
 
 def failed_spike_frames(o, h, l, c, v, qv, p: SpikeParams | None = None, *, first_t=None, lens=None, from_t=None,
-                        exact: bool = True, columns=SPIKE_FRAME_KEYS) -> dict[str, torch.Tensor]:
+                        exact: bool = True, columns=SPIKE_FRAME_KEYS,
+                        frame_cap: int | None = None) -> dict[str, torch.Tensor]:
     """FailedSpikeFade.latest_signal() at EVERY candle of an [S, T] panel:
     column t of row s = the method on a fresh instance (the live behaviour: a
     new strategy instance per message, so the price floor is no running
@@ -681,9 +693,23 @@ def failed_spike_frames(o, h, l, c, v, qv, p: SpikeParams | None = None, *, firs
     SpikeParams range (windows <= 30, cumulative_price_window >= 2, the dynamic
     price break, the three label modes), post_spike_cooldown_bars < 64, and T
     <= engine.SPIKE_FRAMES_MAX_T candles (five times the live store's frame
-    cap); ValueError outside it. A sliding frame cap (a frame that starts
-    later as t grows) is not formed: every frame of a row starts at first_t.
-    Allocates by shape only and reads nothing back (graph-capturable)."""
+    cap); ValueError outside it. Allocates by shape only and reads nothing
+    back (graph-capturable).
+
+    frame_cap = M (64 .. engine.SPIKE_FRAMES_MAX_T): the SLIDING frame of the
+    live store — column t is the method on df.iloc[max(first_t[s], t + 1 -
+    M):t + 1], at most M rows whose first row moves with every candle (the
+    candle provider's LIMIT less the warm-up rows post_process drops). The
+    calibration's two quantiles then run over the frame's own observations
+    (volume_ratio from its row base_window - 1 on, price_change_abs after its
+    first valid close), the columns near the frame's start are the frame's
+    own and the cooldown walk stops at its first row (engine.spike_frames'
+    docstring, the header's rule table). Rows deeper in a frame are the
+    row's columns, which pandas would sum from the frame's first row:
+    thresholds within 1e-9 relative of the class's (observed ~1e-15), flags
+    equal wherever no comparison is a near-tie; exact= keeps its meaning for
+    the column stage. T is not limited under a cap; frame_cap >= T is the
+    uncapped call, bit for bit."""
     p = p or SpikeParams()
     unknown = [k for k in columns if k not in SPIKE_FRAME_KEYS]
     if unknown:
@@ -696,7 +722,11 @@ def failed_spike_frames(o, h, l, c, v, qv, p: SpikeParams | None = None, *, firs
         raise ValueError(f"failed_spike_frames: base_window, streak_length and accel_volume_deriv_window must be in "
                          f"1..30, got {(w, n, aw)}")
     S, T = engine._replay_shape(c)
-    if T > engine.SPIKE_FRAMES_MAX_T:
+    if frame_cap is not None:
+        engine.spike_frames_cap(p, frame_cap)
+        if frame_cap >= T:   # no frame slides
+            frame_cap = None
+    if frame_cap is None and T > engine.SPIKE_FRAMES_MAX_T:
         raise ValueError(f"failed_spike_frames: T = {T} exceeds the cap of {engine.SPIKE_FRAMES_MAX_T} candles per row")
     engine._replay_panels(((o, "open"), (h, "high"), (l, "low"), (c, "close"), (v, "volume"),
                            (qv, "quote_asset_volume")), S, T)
@@ -706,9 +736,9 @@ def failed_spike_frames(o, h, l, c, v, qv, p: SpikeParams | None = None, *, firs
     if aligned:
         first_t = first_t.to(device=c.device, dtype=torch.int64)
         o, c, v = (_frame_aligned(x, first_t) for x in (o, c, v))
-    cols = spike_frame_columns(o, c, v, p, exact)
+    cols = spike_frame_columns(o, c, v, p, exact, cap=frame_cap is not None)
     out = engine.spike_frames(cols, p, first_t=first_t, lens=lens, from_t=from_t, aligned=aligned,
-                              columns=tuple(k for k in columns if k != "close_open_ratio"))
+                              columns=tuple(k for k in columns if k != "close_open_ratio"), frame_cap=frame_cap)
     if "close_open_ratio" in columns:
         cor = cols["close_open_ratio"]
         if aligned:   # back onto the panel's candles

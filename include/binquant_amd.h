@@ -58,6 +58,8 @@
  *                         (strategies/failed_spike_fade.py:596-695)
  *   bq_spike_frames    <- FailedSpikeFade.latest_signal() on every frame of a row, a fresh
  *                         instance per frame (strategies/failed_spike_fade.py:229-594)
+ *   bq_spike_frames_capped <- the same on the live store's sliding frame: at most
+ *                         frame_cap rows, the first row moving with every candle
  *   bq_price_tracker_replay <- PriceTracker.signal(): the null gate, the oversold test,
  *                         the context score's rejections and the entry cooldown
  *                         (strategies/coinrule/price_tracker.py:83-99, :165-251)
@@ -563,6 +565,71 @@ int bq_spike_frames(const double* const* in, int64_t ld_in, const uint8_t* const
                     const int64_t* lens, const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
                     const bq_spike_frames_params* params, void* workspace, size_t workspace_bytes, double* vcmr,
                     double* pbbt, uint8_t* const* out_b, int64_t ld_out, void* stream);
+
+/*
+ * bq_spike_frames under a SLIDING frame cap: column t of row s is
+ * FailedSpikeFade.latest_signal() of a fresh instance whose frame is
+ * df.iloc[f:t + 1], f = max(first, t + 1 - frame_cap), with a RangeIndex, and
+ * the instance's two calibrated thresholds. This is what the live system
+ * sees: the candle provider refetches the last LIMIT candles per message and
+ * post_process drops the warm-up rows, so a frame's first row moves with every
+ * candle. T is not limited by BQ_SPIKE_FRAMES_MAX_T: a frame's sorted keys (at
+ * most frame_cap per column) live in LDS, whatever T.
+ *
+ * in, in_b, aligned, lens, first_t, from_t, params, the outputs and their
+ * conventions are bq_spike_frames': the columns as a frame starting at `first`
+ * forms them. in_i [BQ_NUM_SPIKE_FRAMES_IN_I] int32 [S][ld_i], indexed like
+ * `in` and holding column indices of `in`: dyn_src, the column of the
+ * forward-filled rolling quantile's source (the last column at or before it
+ * whose unfilled quantile is not NaN; -1: none), and close_next, the first
+ * column at or after it whose close is not NaN (T: none). cap: frame_cap and
+ * the three parameters of detect() that only the frame-local columns need.
+ *
+ * What is frame-local, for a frame [f, t] with f > first; g = close_next[f],
+ * the frame's first valid close (rows are candles):
+ *   volume_ratio            NaN on rows < f + base_window - 1: no observation
+ *                           of the calibration, no bit of the cluster count or
+ *                           of vol_cond there
+ *   price_change(_abs)      NaN on rows <= g (the pad fill has no source in the
+ *                           frame): an observation of the calibration from row
+ *                           g + 1 on, price_break_flag False on rows <= g
+ *   vol_cond                True on rows < f + cumulative_price_window - 1
+ *   the clip sums           NaN on rows < g + cumulative_price_window
+ *   the acceleration flags  False on rows <= g and on rows < f + base_window
+ *                           - 1 + accel_volume_deriv_window
+ *   the rolling(60, min_periods=20) quantile of price_change_abs
+ *                           rows >= g + 60: the input's. Rows < g + 60, and
+ *                           every later row whose fill's source lies before
+ *                           g + 60: roll_quantile of rows g + 1 .. min(row,
+ *                           g + 59), NaN below 20 observations
+ *   apply_cooldown          walks rows f .. t
+ * Every other row of the frame has the input's columns; pandas would form its
+ * rolling mean and sums from row f, so they agree to running-sum rounding
+ * (the thresholds to ~1e-15 relative, the bytes wherever no comparison is a
+ * near-tie). With 1 <= base_window, accel_volume_deriv_window <= 30 and the
+ * windows of params a full frame's newest row t = f + frame_cap - 1 >= f + 63
+ * lies past every rule above but the quantile's when g > f + 3.
+ *
+ * workspace: bq_spike_frames_capped_workspace(S, T) bytes, 8-byte aligned.
+ * BQ_EINVAL, before any launch: bq_spike_frames' conditions except the one on
+ * T; cap NULL, frame_cap outside 64 .. BQ_SPIKE_FRAMES_MAX_T, base_window or
+ * accel_volume_deriv_window outside 1 .. BQ_SPIKE_FRAMES_MAX_WINDOW,
+ * price_break_dynamic_q outside [0, 1]; in_i NULL or with a NULL entry, ld_i <
+ * T; T > 2^30. Two launches, nothing allocated.
+ */
+#define BQ_SPIKE_FRAMES_MIN_CAP 64
+typedef struct bq_spike_frames_cap {
+  int32_t frame_cap, base_window, accel_volume_deriv_window, reserved;
+  double price_break_dynamic_q;
+} bq_spike_frames_cap;
+enum bq_spike_frames_in_i { BQ_SF_DYN_SRC = 0, BQ_SF_CLOSE_NEXT, BQ_NUM_SPIKE_FRAMES_IN_I };
+size_t bq_spike_frames_capped_workspace(int64_t S, int64_t T);
+int bq_spike_frames_capped(const double* const* in, int64_t ld_in, const uint8_t* const* in_b, int64_t ld_b,
+                           const int32_t* const* in_i, int64_t ld_i, int32_t aligned, const int64_t* lens,
+                           const int64_t* first_t, const int64_t* from_t, int64_t S, int64_t T,
+                           const bq_spike_frames_params* params, const bq_spike_frames_cap* cap, void* workspace,
+                           size_t workspace_bytes, double* vcmr, double* pbbt, uint8_t* const* out_b, int64_t ld_out,
+                           void* stream);
 
 /*
  * PriceTracker.signal() replayed over a panel of 5m frames

@@ -81,6 +81,8 @@ rows = {
     "failed_spike": lambda: strategies.failed_spike_features(o, h, l, c, v, qv),
     # FailedSpikeFade.latest_signal() at every candle: the column stage and bq_spike_frames (T <= 2048)
     "failed_spike_frames": lambda: strategies.failed_spike_frames(o, h, l, c, v, qv),
+    # the same under the live store's sliding frame of 301 rows: bq_spike_frames_capped (any T)
+    "failed_spike_frames_cap301": lambda: strategies.failed_spike_frames(o, h, l, c, v, qv, frame_cap=301),
     "wilder_rsi": lambda: signals.wilder_rsi(c),
     "adx": lambda: signals.adx(h, l, c),
     "zscore": lambda: signals.zscore(c),
