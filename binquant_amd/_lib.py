@@ -61,6 +61,11 @@ STORE_MAX_BARS = 512
 MICRO_REGIMES = ("TREND_UP", "TREND_DOWN", "RANGE", "VOLATILE", "TRANSITIONAL")
 MICRO_TRANSITIONS = ("VOLATILITY_EXPANSION", "BREAKOUT_UP", "BREAKDOWN", "RECOVERY", "MEAN_REVERSION",
                      "ENTERED_TREND_UP", "ENTERED_TREND_DOWN", "ENTERED_RANGE", "ENTERED_TRANSITIONAL")
+# bq_symbol_regime_panel's output columns, the order of bq_regime_panel_u8 / bq_regime_panel_f64
+REGIME_PANEL_U8 = ("ok", "micro_regime", "micro_transition", "above_ema20", "above_ema50")
+REGIME_PANEL_F64 = ("rs_vs_btc", "micro_regime_strength", "micro_transition_strength", "trend_score", "atr_pct",
+                    "bb_width")
+REGIME_PANEL_COLUMNS = REGIME_PANEL_U8 + REGIME_PANEL_F64
 SCORE_FIELDS = ("confidence", "breadth_score", "btc_alignment_score", "cross_asset_confirmation",
                 "followthrough_score", "adverse_excursion_risk", "override_strength", "supportiveness_score",
                 "adjusted_score")
@@ -612,6 +617,8 @@ SIGNATURES: dict[str, tuple] = {
     "bq_zscore": (ctypes.c_int, [_P, _I64, _I64, _I64, _I32, _P, _I64, _P]),
     "bq_adx": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _P, _I64, _P]),
     "bq_micro_regime": (ctypes.c_int, [_I64] + [_P] * 13 + [_P]),
+    "bq_symbol_regime_panel": (ctypes.c_int, [_PP, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P,
+                                              _PP, _I64, _PP, _I64, _P]),
     "bq_context_score": (ctypes.c_int, [_I64, _P, _P, _P, _P, ctypes.POINTER(BqContextScalars),
                                         ctypes.POINTER(BqScorerWeights), _P, _I64, _P]),
     "bq_cohort_select": (ctypes.c_int, [_I64, _P, _P, _P, _P, _I32, _P, _P, _P]),

@@ -761,6 +761,100 @@ def breadth_partial_fresh(
     return out
 
 
+REGIME_PANEL_COLUMNS = _lib.REGIME_PANEL_COLUMNS
+
+
+def _panel_index(x, name: str, n, lo: int, hi: int, dev) -> torch.Tensor:
+    """at / prev of symbol_regime_panel: a 1-D integer array (numpy or torch, host or device) of n entries (n None:
+    any length) with values in lo .. hi, as a contiguous int32 tensor on dev."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(x)
+    want = "" if n is None else f" of shape {(n,)}"
+    if x.dim() != 1 or x.dtype not in (torch.int32, torch.int64) or (n is not None and x.shape[0] != n):
+        raise ValueError(f"{name}: expected a 1-D int32 / int64 tensor{want}")
+    if x.numel() and (int(x.min()) < lo or int(x.max()) > hi):
+        raise ValueError(f"{name}: values in {lo}..{hi} (context columns), got {int(x.min())}..{int(x.max())}")
+    return x.to(device=dev, dtype=torch.int32).contiguous()
+
+
+@device_entry
+def symbol_regime_panel(feats: dict[str, torch.Tensor], close: torch.Tensor, *, rank: torch.Tensor | None = None,
+                        at=None, prev=None, btc_return: torch.Tensor | None = None, btc_row: int | None = None,
+                        seed=None, columns=REGIME_PANEL_COLUMNS) -> dict[str, torch.Tensor]:
+    """The symbol_features entry every candle of a panel saw, for all symbols
+    at once (bq_symbol_regime_panel): RegimeTransitionDetector.annotate_context
+    (market_regime/regime_transitions.py:25-43, :162-232) over the feature
+    columns of a context build. feats: the six FEATURE_COLUMNS [S, Tc] float64
+    on one row stride, and close [S, Tc] they were computed from (a fresh
+    build: CompactPanel.close, with rank = CompactPanel.rank, int32 [S, Tc]).
+    at int [T_out]: the context column candle t sees (-1: none; default
+    arange(Tc)); prev int [T_out]: the column stored before it (-1: none, -2:
+    the seed; default at - 1). btc_return float64 [Tc]: BTC's return_pct per
+    context column, NaN where it has no features (None: nowhere), btc_row its
+    row (its own relative strength stays 0.0). seed: (int8 [S] micro-regime
+    codes, negative None; float64 [S] strengths) of the snapshot before the
+    panel's first context. Returns {name: [S, T_out]} for `columns`, a subset
+    of REGIME_PANEL_COLUMNS: uint8 ok / micro_regime / micro_transition
+    (indices into _lib.MICRO_REGIMES / MICRO_TRANSITIONS, _lib.MR_NONE for
+    None) / above_ema20 / above_ema50, float64 rs_vs_btc /
+    micro_regime_strength / micro_transition_strength / trend_score / atr_pct
+    / bb_width (NaN where ok is 0). Columns left out are neither computed nor
+    allocated."""
+    columns = tuple(columns)
+    _replay_columns("symbol_regime_panel", columns, REGIME_PANEL_COLUMNS)
+    S, Tc = _replay_shape(close)
+    missing = [n for n in FEATURE_COLUMNS if n not in feats]
+    if missing:
+        raise ValueError(f"feats: missing {missing} (expected {FEATURE_COLUMNS})")
+    cols = [(feats[n], n) for n in FEATURE_COLUMNS] + [(close, "close")]
+    _replay_panels(cols, S, Tc)
+    for x, name in cols:
+        if Tc > 1 and x.stride(1) != 1:
+            raise ValueError(f"{name}: expected [S, T] with unit stride along T")
+    ld_f = _row_stride(cols[0][0])
+    if any(_row_stride(x) != ld_f for x, _ in cols[1:len(FEATURE_COLUMNS)]):
+        raise ValueError("feature columns must share one row stride")
+    if rank is not None and not (isinstance(rank, torch.Tensor) and rank.dtype == torch.int32
+                                 and tuple(rank.shape) == (S, Tc) and (Tc <= 1 or rank.stride(1) == 1)):
+        raise ValueError(f"rank: expected an int32 tensor of shape {(S, Tc)} with unit stride along T")
+    dev = close.device
+    if at is None:
+        at_d = torch.arange(Tc, dtype=torch.int32, device=dev)
+    else:
+        at_d = _panel_index(at, "at", None, -1, Tc - 1, dev)
+    T_out = int(at_d.shape[0])
+    if prev is None:
+        prev_d = (at_d - 1).clamp_(min=-1)
+    else:
+        prev_d = _panel_index(prev, "prev", T_out, -2, Tc - 1, dev)
+    if btc_return is not None and not (isinstance(btc_return, torch.Tensor) and btc_return.dtype == torch.float64
+                                       and tuple(btc_return.shape) == (Tc,)):
+        raise ValueError(f"btc_return: expected a float64 tensor of shape {(Tc,)}")
+    if btc_row is not None and not (isinstance(btc_row, int) and 0 <= btc_row < S):
+        raise ValueError(f"btc_row: expected None or a row in 0..{S - 1}, got {btc_row}")
+    if seed is not None and not (len(seed) == 2 and all(isinstance(x, torch.Tensor) for x in seed)
+                                 and seed[0].dtype == torch.int8 and seed[1].dtype == torch.float64
+                                 and all(tuple(x.shape) == (S,) and x.is_contiguous() for x in seed)):
+        raise ValueError(f"seed: expected (micro_regime int8, micro_regime_strength float64) contiguous tensors of "
+                         f"shape {(S,)}")
+    sr, ss = seed if seed is not None else (None, None)
+    _replay_on_device("symbol_regime_panel", [x for x, _ in cols] + [rank, btc_return, sr, ss])
+    if btc_return is None:
+        btc_return = torch.full((Tc,), float("nan"), dtype=torch.float64, device=dev)
+    btc_return = btc_return.contiguous()
+    out = {k: torch.empty((S, T_out), dtype=torch.uint8 if k in _lib.REGIME_PANEL_U8 else torch.float64, device=dev)
+           for k in columns}
+    st = _lib.load().bq_symbol_regime_panel(
+        _lib.ptr_array([x.data_ptr() for x, _ in cols[:len(FEATURE_COLUMNS)]]), ld_f, _ptr(close),
+        _row_stride(close), _ptr(rank), _row_stride(rank) if rank is not None else 0, S, Tc, _ptr(at_d), _ptr(prev_d),
+        T_out, _ptr(btc_return), -1 if btc_row is None else btc_row, _ptr(sr), _ptr(ss),
+        _lib.ptr_array([out[k].data_ptr() if k in out else 0 for k in _lib.REGIME_PANEL_U8]), T_out,
+        _lib.ptr_array([out[k].data_ptr() if k in out else 0 for k in _lib.REGIME_PANEL_F64]), T_out,
+        _stream_handle(None))
+    _lib.check(st, "bq_symbol_regime_panel")
+    return out
+
+
 @device_entry
 def context_partials(
     high: torch.Tensor,

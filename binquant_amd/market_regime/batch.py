@@ -25,8 +25,47 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .. import engine
+from .. import _lib, engine
 from .regime import ContextBatch, annotate_market, annotate_symbols, score_contexts
+
+
+def seen_columns(valid, timestamps, carry: bool = True, times=None, seeded: bool = False):
+    """(at, prev) int64 [T_out] of MarketContextBatch.snapshot, O(T) on the
+    host: at[t] the context column candle t sees (-1: none) and prev[t] the
+    latest valid column before it (-1: none; -2: the seed, when seeded).
+    carry: the latest valid context at or before the candle (the provider's
+    latest_market_context), else only the candle's own. times: None (the
+    frame is on the contexts' grid) or int64 [T_out] candle close times: the
+    latest valid context with timestamp <= time (carry=False: == time)."""
+    valid = np.asarray(valid, dtype=bool)
+    Tc = len(valid)
+    cols = np.arange(Tc, dtype=np.int64)
+    last_valid = np.maximum.accumulate(np.where(valid, cols, -1)) if Tc else cols
+    before = np.concatenate([[-1], last_valid[:-1]]) if Tc else cols   # the latest valid column before j
+    if times is None:
+        at = last_valid if carry else np.where(valid, cols, -1)
+    else:
+        ts = np.asarray(timestamps, dtype=np.int64)
+        if Tc > 1 and not (np.diff(ts) > 0).all():
+            raise ValueError("snapshot: times= needs ascending context timestamps")
+        times = np.asarray(times.cpu() if isinstance(times, torch.Tensor) else times)
+        if times.ndim != 1 or times.dtype != np.int64:
+            raise ValueError("times: expected a 1-D int64 array of candle close times")
+        if not Tc:
+            at = np.full(len(times), -1, dtype=np.int64)
+        else:
+            pos = np.searchsorted(ts, times, side="right") - 1
+            safe = np.maximum(pos, 0)
+            if carry:
+                at = np.where(pos >= 0, last_valid[safe], -1)
+            else:
+                at = np.where((pos >= 0) & (ts[safe] == times) & valid[safe], safe, -1)
+    at = np.asarray(at, dtype=np.int64)
+    seen = at >= 0
+    prev = np.where(seen, before[np.maximum(at, 0)], -1) if Tc else np.full(len(at), -1, dtype=np.int64)
+    if seeded:
+        prev = np.where(seen & (prev < 0), -2, prev)
+    return at, np.asarray(prev, dtype=np.int64)
 
 
 @dataclass
@@ -35,6 +74,7 @@ class MarketContextBatch:
     features: dict[str, torch.Tensor]   # this rank's [S, T] feature columns
     partial: torch.Tensor               # reduced [T, 10] partials (device)
     rank: torch.Tensor | None = None    # fresh build: [S, T] int32 column of each candle in `features`
+    compact_close: torch.Tensor | None = None   # fresh build: the packed close `features` were computed from
 
     def context_at(self, i: int) -> dict | None:
         return self.contexts.context_at(i)
@@ -76,6 +116,126 @@ class MarketContextBatch:
         out.update(annotate_symbols(f["trend_score"], out["above_ema20"], out["above_ema50"], rs,
                                     f["bb_width"], f["atr_pct"], ret))
         return out
+
+    def snapshot(self, close: torch.Tensor, *, btc_index: int | None = None, carry: bool = True, times=None,
+                 seed=None, columns=engine.REGIME_PANEL_COLUMNS) -> "PanelSnapshot":
+        """What every candle of a panel saw of these contexts, on the device:
+        the context's fields and each symbol's symbol_features entry with its
+        micro regime and transition (engine.symbol_regime_panel), ready for the
+        signals.*_entry panel entries. close: the panel's [S, T] close the
+        build was given (this rank's symbols). btc_index: BTC's row, if the
+        shard holds it. carry=True: a candle sees the latest valid context at
+        or before it (KlinesProvider.latest_market_context,
+        consumers/klines_provider.py:181-199); carry=False: only its own
+        (accumulator.get_context(ts)). times: int64 [T_out] candle close times
+        of a frame on another grid (the 5m frame against 15m contexts): a
+        candle then sees the latest valid context with timestamp <= its time
+        (carry=False: the one with that very timestamp). A context's
+        predecessor is the latest valid one before it (_get_previous_context,
+        live_market_context_accumulator.py:86-93); the first valid context has
+        none unless `seed` is given: (int8 [S] micro-regime codes, negative
+        None; float64 [S] strengths), the symbols' entries in the
+        previous_context the build was seeded with. The host part is O(T)
+        numpy over contexts.valid / contexts.timestamp; rows are independent,
+        so a symbol shard needs nothing beyond its replicated BTC row."""
+        valid = np.asarray(self.contexts.valid, dtype=bool)
+        Tc = len(valid)
+        fcols = next(iter(self.features.values())).shape[1]
+        if fcols != Tc:
+            raise ValueError("snapshot: a fused context build (keep_features=False) keeps no feature columns")
+        if self.rank is not None and self.compact_close is None:
+            raise ValueError("snapshot: a fresh build needs compact_close, the packed close of its features")
+        at, prev = seen_columns(valid, self.contexts.timestamp, carry=carry, times=times, seeded=seed is not None)
+        f = self.contexts.fields
+        dev = close.device
+        btc = torch.from_numpy(np.where(f["btc_present"], f["btc_return"], np.nan).astype(np.float64)).to(dev)
+        sym = engine.symbol_regime_panel(
+            self.features, close if self.rank is None else self.compact_close, rank=self.rank, at=at, prev=prev,
+            btc_return=btc, btc_row=btc_index, seed=seed, columns=columns)
+        return PanelSnapshot(contexts=self.contexts, at=at, columns=sym, device=dev)
+
+
+_CTX_CODED = {"market_regime", "regime_is_transitioning", "confidence"}
+
+
+@dataclass
+class PanelSnapshot:
+    """MarketContextBatch.snapshot's result: per candle of the frame, the
+    context it saw (`at`: its column in `contexts`, -1 for none) and, per
+    symbol, that context's symbol_features entry (`columns`,
+    engine.symbol_regime_panel's tensors [S, T_out])."""
+
+    contexts: ContextBatch
+    at: np.ndarray
+    columns: dict[str, torch.Tensor]
+    device: torch.device
+
+    def _gathered(self, values: np.ndarray, none) -> np.ndarray:
+        seen = self.at >= 0
+        out = np.full(len(self.at), none, dtype=values.dtype)
+        out[seen] = values[self.at[seen]]
+        return out
+
+    @property
+    def ok(self) -> torch.Tensor:
+        """bool [T_out]: a context is seen (the entries' ctx_ok)."""
+        return torch.from_numpy(self.at >= 0).to(self.device)
+
+    def ctx(self, rows) -> torch.Tensor:
+        """float64 [len(rows), T_out] on the device: the seen context's fields,
+        NaN where `ok` is false. rows: any of _lib.PT_CTX_ROWS / MR_CTX_ROWS /
+        RF_CTX_ROWS / GL_CTX_ROWS and ContextBatch's numeric fields;
+        market_regime is the index into _lib.MARKET_REGIMES,
+        regime_is_transitioning 0 / 1, confidence 1.0
+        (live_market_context_accumulator.py:213)."""
+        f = self.contexts.fields
+        out = np.empty((len(rows), len(self.at)), dtype=np.float64)
+        for i, name in enumerate(rows):
+            if name == "confidence":
+                v = np.ones(len(self.contexts.valid))
+            elif name == "market_regime":
+                v = np.array([_lib.MARKET_REGIMES.index(r) for r in f[name]], dtype=np.float64)
+            elif name in f and np.asarray(f[name]).dtype.kind in "fiub":
+                v = np.asarray(f[name], dtype=np.float64)
+            else:
+                known = sorted(_CTX_CODED | {k for k, a in f.items() if np.asarray(a).dtype.kind in "fiub"})
+                raise ValueError(f"ctx: unknown row {name!r} (known: {known})")
+            out[i] = self._gathered(v, np.nan)
+        return torch.from_numpy(out).to(self.device)
+
+    def sym(self, keys, none: str = "uint8") -> dict[str, torch.Tensor]:
+        """{key: [S, T_out]} for signals.*_entry(sym=...) and the *_routing /
+        *_allows helpers. none="uint8": ok uint8 and micro_regime /
+        micro_transition uint8 with _lib.MR_NONE for None (the *_entry
+        convention); none="int8": ok bool and the two codes int8, negative for
+        None (the helpers' convention)."""
+        if none not in ("uint8", "int8"):
+            raise ValueError(f"sym: none is 'uint8' (_lib.MR_NONE) or 'int8' (negative), got {none!r}")
+        missing = [k for k in keys if k not in self.columns]
+        if missing:
+            raise ValueError(f"sym: {missing} not among the snapshot's columns {tuple(self.columns)}")
+        out = {k: self.columns[k] for k in keys}
+        if none == "int8":
+            for k in keys:
+                if k in ("micro_regime", "micro_transition"):
+                    x = out[k]
+                    out[k] = torch.where(x == _lib.MR_NONE, -1, x.to(torch.int16)).to(torch.int8)
+                elif k == "ok":
+                    out[k] = out[k].bool()
+        return out
+
+    @property
+    def timestamp(self) -> torch.Tensor:
+        """int64 [T_out]: the seen context's timestamp (ms), -1 where none."""
+        return torch.from_numpy(self._gathered(np.asarray(self.contexts.timestamp, dtype=np.int64), -1)).to(self.device)
+
+    @property
+    def regime_stable_since(self) -> torch.Tensor:
+        """int64 [T_out]: the seen context's regime_stable_since (ms),
+        negative for None (signals.long_autotrade_allows, bb_extreme_routing)."""
+        ss = self.contexts.fields["regime_stable_since"]
+        v = np.array([-1 if x is None else int(x) for x in ss], dtype=np.int64)
+        return torch.from_numpy(self._gathered(v, -1)).to(self.device)
 
 
 def shard_bounds(n_symbols: int, world: int, rank: int) -> tuple[int, int]:
@@ -143,11 +303,11 @@ def contexts_from_partials(partial: np.ndarray, btc_return: np.ndarray, btc_tren
 
 
 def _scored(part, btc_ret, btc_trend, total_tracked, timestamps, previous_context, feats,
-            rank=None) -> MarketContextBatch:
+            rank=None, compact_close=None) -> MarketContextBatch:
     """The tail of both builds: host scoring of the reduced partials."""
     batch = contexts_from_partials(part.cpu().numpy(), btc_ret, btc_trend, total_tracked=total_tracked,
                                    timestamps=timestamps, previous_context=previous_context)
-    return MarketContextBatch(contexts=batch, features=feats, partial=part, rank=rank)
+    return MarketContextBatch(contexts=batch, features=feats, partial=part, rank=rank, compact_close=compact_close)
 
 
 def _market_context_batch_fresh(high, low, close, btc_hlc, max_bars, timestamps, total_tracked, group,
@@ -168,7 +328,7 @@ def _market_context_batch_fresh(high, low, close, btc_hlc, max_bars, timestamps,
     btc_ret = np.where(have, bf["return_pct"][0].cpu().numpy()[kk], np.nan)
     btc_trend = np.where(have, bf["trend_score"][0].cpu().numpy()[kk], np.nan)
     return _scored(part, btc_ret, btc_trend, total_tracked if total_tracked is not None else tracked, timestamps,
-                   previous_context, feats, comp.rank)
+                   previous_context, feats, comp.rank, comp.close)
 
 
 def market_context_batch(

@@ -42,6 +42,8 @@
  *   bq_parse_kline_events <- json.loads + KlineProduceModel of the websocket
  *                         frames, producers/klines_connector.py:77-164 (host)
  *   bq_micro_regime    <- regime_transitions.py:162-232 (per-symbol micro regime)
+ *   bq_symbol_regime_panel <- the same with annotate_context's predecessor rule
+ *                         (regime_transitions.py:25-43) at every candle of a panel
  *   bq_context_score   <- context_scoring.py:13-114 + signal_context_scorer.py:15-55
  *   bq_cohort_select   <- the portfolio selectors' winner pick
  *                         (liquidation_sweep_pump.py:38-87, gradual_gainer_retest.py:33-70)
@@ -2064,6 +2066,48 @@ int bq_micro_regime(int64_t n, const double* trend, const uint8_t* above_ema20, 
                     const double* rs, const double* bb_width, const double* atr_pct, const double* return_pct,
                     const int8_t* prev_regime, const double* prev_strength, int8_t* regime, double* strength,
                     int8_t* transition, double* transition_strength, void* stream);
+
+/*
+ * The per-symbol regime panel: for every candle t of a [S][T_out] panel, the
+ * symbol_features entry of symbol s in the market context that candle saw
+ * (KlinesProvider.latest_market_context + resolve_symbol_features), with the
+ * micro regime and transition of RegimeTransitionDetector.annotate_context
+ * (regime_transitions.py:25-43, :162-232) against the context stored
+ * immediately before the seen one. One streaming pass; stream-ordered; no
+ * atomics (bitwise reproducible).
+ *
+ * feat[BQ_NUM_FEATURES] [S][ld_f] and close [S][ld_c]: the feature columns of
+ * a context build and the close they were computed from, Tc columns each.
+ * rank: NULL (dense build: symbol s has features at context column j iff
+ * j >= 1, its feature column is j) or [S][ld_r] int32 of a fresh build
+ * (bq_panel_compact: with k = rank[s][j] the symbol has features iff k >= 1,
+ * its feature column is k; feat / close are then the packed ones).
+ * at[T_out] int32: the context column candle t sees, negative for none.
+ * prev[T_out] int32: the context column stored before at[t]; -1 none, -2 the
+ * seed (seed_regime int8 [S], negative = None, and seed_strength [S]; either
+ * may be NULL: None / 0.0). btc_return[Tc]: BTC's return_pct in context
+ * column j, NaN where BTC has no features (every rs is then 0.0); btc_row:
+ * BTC's row (its own rs stays 0.0) or -1.
+ *
+ * out_u8[BQ_RP_NUM_U8] [S][ld_u8] and out_f64[BQ_RP_NUM_F64] [S][ld_f64], in
+ * the enums' order; a NULL entry is neither computed nor written. Where the
+ * symbol has no features in the seen context (or no context is seen): ok 0,
+ * the codes 255, the flags 0, the values NaN. micro_regime / micro_transition
+ * index bq_micro_regime_code / bq_micro_transition_code (255 = None).
+ * Tc, T_out <= 2^31 - 257; S * ceil(T_out / 256) <= 2^31 - 1.
+ */
+enum bq_regime_panel_u8 {
+  BQ_RP_OK = 0, BQ_RP_MICRO_REGIME, BQ_RP_MICRO_TRANSITION, BQ_RP_ABOVE_EMA20, BQ_RP_ABOVE_EMA50, BQ_RP_NUM_U8
+};
+enum bq_regime_panel_f64 {
+  BQ_RP_RS_VS_BTC = 0, BQ_RP_REGIME_STRENGTH, BQ_RP_TRANSITION_STRENGTH, BQ_RP_TREND_SCORE, BQ_RP_ATR_PCT,
+  BQ_RP_BB_WIDTH, BQ_RP_NUM_F64
+};
+int bq_symbol_regime_panel(const double* const* feat, int64_t ld_f, const double* close, int64_t ld_c,
+                           const int32_t* rank, int64_t ld_r, int64_t S, int64_t Tc, const int32_t* at,
+                           const int32_t* prev, int64_t T_out, const double* btc_return, int64_t btc_row,
+                           const int8_t* seed_regime, const double* seed_strength, uint8_t* const* out_u8,
+                           int64_t ld_u8, double* const* out_f64, int64_t ld_f64, void* stream);
 
 enum bq_direction { BQ_DIR_LONG = 0, BQ_DIR_SHORT = 1, BQ_DIR_OTHER = 2 };   /* direction.upper().strip() */
 typedef struct bq_context_scalars {   /* the LiveMarketContext fields the scorer reads */

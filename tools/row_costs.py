@@ -52,6 +52,16 @@ def price_tracker_cols():
     return _pt["args"]
 
 
+_mf: dict = {}
+
+
+def market_feature_cols():
+    """The context build's six feature columns, computed once."""
+    if not _mf:
+        _mf.update(engine.market_features(h, l, c, max_bars=400))
+    return _mf
+
+
 def timeit(fn, reps=3):
     fn()
     torch.cuda.synchronize()
@@ -120,6 +130,11 @@ rows = {
              "above_ema50": torch.ones(S, dtype=torch.uint8, device="cuda"),
              "rs_vs_btc": torch.full((S,), 0.1, dtype=torch.float64, device="cuda"),
              "atr_pct": torch.full((S,), 0.01, dtype=torch.float64, device="cuda")}),
+    # every symbol's symbol_features entry, micro regime and transition at every candle (all eleven columns; a dense
+    # build's feature columns, every context valid, BTC = row 0)
+    "symbol_regime_panel": lambda: engine.symbol_regime_panel(market_feature_cols(), c,
+                                                              btc_return=market_feature_cols()["return_pct"][0],
+                                                              btc_row=0),
     "resample_1h": lambda: engine.resample(ts, {"open": o, "high": h, "low": l, "close": c, "volume": v},
                                            {"open": "first", "high": "max", "low": "min", "close": "last",
                                             "volume": "sum"}, 3_600_000),
